@@ -1,6 +1,6 @@
 """bench.py -- Mkeys/s of the hot path (glu::RadixSort::operator(), reference glu/RadixSort.hpp:273-334) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Both forms work for N > 1: the plain command (no WORLD_SIZE in the environment) starts the second form as a CHILD process
@@ -13,8 +13,11 @@ A "step" is one full sort of one batch of synthetic unsorted input that is alrea
           sits inside the timed region.
   N > 1   BASELINE.json configs[3]: 2^27 pairs per GPU (2^30 at N = 8), rank r holds slice r; top-8-bit bucket
           partition -> one all-to-all (RCCL over xGMI) -> local sort (gl-radix-sort_amd/glu_hip/dist.py).
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the scatter pass) from HIP-event timings
-taken inside the timed region; `cpu_baseline` is std::sort on the host cores over a bounded sample.
+Rank 0 prints ONE JSON line.  At N = 1 a plain run sets up, warms up, times the K steps and prints the line: the headline
+and nothing else.  --full adds what the headline does not need: `roofline` prices the dominant kernel (the scatter pass) from
+HIP-event timings taken inside the timed region; `verified` checks the last step's output; `four_pass_sort` and
+`reference_pass_structure` time the same sort by other pass structures; `cpu_baseline` is std::sort on the host cores.
+--dump-outputs DIR writes the last timed step's output (a seeded sample and block sums, dump_outputs) before any of that.
 For every N, `value` / `ms_per_step` are ONE SORT AT A TIME (K sorts enqueued back to back on one stream), so that the
 1/2/4/8-GPU curve compares like with like; N > 1 also reports the two-sorts-in-flight throughput as `value_depth2` and
 `one_gpu` = this very run's single-GPU figures (2^28 pairs on every rank's own GPU, depth 1 and depth 2), with
@@ -47,6 +50,11 @@ def parse_args():
     p.add_argument("--digit-bits", type=int, default=None, help="4 or 8 (default: library default)")
     p.add_argument("--keys", default="uniform", choices=["uniform", "zero"],
                    help="uniform = headline; zero = the reference README's benchmark input")
+    p.add_argument("--full", action="store_true",
+                   help="N=1: also measure and check what the headline does not need (per-kernel events and roofline, "
+                        "verification, the four-pass and 4-bit sorts, the CPU baseline); the --no-* options below trim it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one gave its caller to DIR/*.npy (float64, see dump_outputs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-log2", type=int, default=None,
                    help="time the CPU baseline on a generated 2^this sample instead of the GPU workload's own array")
@@ -82,7 +90,10 @@ def parse_args():
                    help="NOT a measurement: run the N>1 code path with all ranks on GPU 0 (gloo process group, glu_dist over "
                         "the file transport named by GLU_HIP_RCCL_LIB, tests/cpp/mock_rccl.cpp) to check that the launch, the "
                         "collectives and the JSON line work before an 8-GPU node runs them")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_input(torch, n, kind, seed, device, index_base=0, as_rank_of=1):
@@ -127,6 +138,40 @@ def pair_fingerprint(torch, keys, vals):
     h = (h ^ ((h >> 29) & 0x7FFFFFFFF)) * s64(0xBF58476D1CE4E5B9)
     g = (h ^ ((h >> 32) & 0xFFFFFFFF)) * s64(0x94D049BB133111EB)
     return torch.stack([h.sum(), g.sum()])
+
+
+DUMP_SAMPLE = 1 << 21  # positions sampled per array: 2 x 16 MiB of float64, inside the 64 MB a dump may take
+DUMP_BLOCKS = 4096
+
+
+def dump_outputs(torch, out_dir, keys, vals):
+    """--dump-outputs: the sorted keys and values the caller received, as unsigned 32-bit values in float64 (exact), so that two
+    builds can be compared output for output on the same seeded input.
+      keys.npy, values.npy                  the pairs at a fixed sample of positions (seeded, the same for the same n; every
+                                            position when n <= DUMP_SAMPLE; the first and the last always)
+      keys_block_sums.npy, values_block_sums.npy   sums over DUMP_BLOCKS equal blocks of the whole arrays (zero-padded), so that
+                                            a difference outside the sample still shows"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(keys.shape[0])
+    if n > DUMP_SAMPLE:
+        rng = np.random.default_rng(0xD0)
+        idx = np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, DUMP_SAMPLE)]))
+    else:
+        idx = np.arange(n)
+    idx_dev = torch.from_numpy(idx).to(keys.device)
+    blocks = max(1, min(DUMP_BLOCKS, n))
+    per_block = -(-n // blocks)
+    for name, a in (("keys", keys), ("values", vals)):
+        u = a.to(torch.int64) & 0xFFFFFFFF
+        np.save(os.path.join(out_dir, name + ".npy"), u[idx_dev].cpu().numpy().astype(np.float64))
+        padded = torch.zeros(blocks * per_block, dtype=torch.int64, device=a.device)
+        padded[:n] = u
+        del u
+        sums = padded.view(blocks, per_block).sum(1)  # < 2^32 * per_block: exact in float64 up to n = 2^33
+        np.save(os.path.join(out_dir, name + "_block_sums.npy"), sums.cpu().numpy().astype(np.float64))
+        del padded
 
 
 def cpu_baseline(sample_log2, keys_host=None, vals_host=None):
@@ -393,14 +438,17 @@ def main():
         for i in range(W):
             step(i)
         barrier()
-        # LIGHT per-kernel events in the timed region: only around the kernels that move the data (the scatter of every pass
-        # that is expected to run, the in-LDS pass) -- an event between two kernels costs the queue microseconds, and all 28 of
-        # a sort that ends in LDS were 4 % of its time; count / scan kernel times come from three more sorts after the region
-        sorter.set_profiling(False if args.no_kernel_events else (True if args.full_kernel_events else "light"))
+        # --full: LIGHT per-kernel events in the timed region: only around the kernels that move the data (the scatter of every
+        # pass that is expected to run, the in-LDS pass) -- an event between two kernels costs the queue microseconds, and all 28
+        # of a sort that ends in LDS were 4 % of its time; count / scan kernel times come from three more sorts after the region.
+        # A plain run records no event: its timed region holds the K sorts alone.
+        events = args.full and not args.no_kernel_events
+        if events:
+            sorter.set_profiling(True if args.full_kernel_events else "light")
         step_events = []
         t0 = time.perf_counter()
         for i in range(W, W + K):
-            if not args.no_kernel_events:  # per-step device time (every step sorts a differently placed copy)
+            if events:  # per-step device time (every step sorts a differently placed copy)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(work_stream)
                 step(i)
@@ -410,192 +458,196 @@ def main():
                 step(i)
         barrier()
         elapsed = time.perf_counter() - t0
-        step_ms = sorted(a.elapsed_time(b) for a, b in step_events)
-        prof = sorter.read_profile()
-        sorter.set_profiling(False)
-        detail = {"count_ms": 0.0, "scan_ms": 0.0, "passes": 0}
-        if not args.no_kernel_events:  # (outside the timed region: every kernel boundary of three more sorts)
-            sorter.set_profiling(True)
-            for i in range(W + K, W + K + 3):
-                k, v = sets[i % copies]
-                k.copy_(keys0)
-                v.copy_(vals0)
-                sorter.run_ptr(k.data_ptr(), v.data_ptr(), n, 0, stream)
-            torch.cuda.synchronize()
-            detail = sorter.read_profile()
-            sorter.set_profiling(False)
-        bits = sorter.digit_bits
         units = n * K
-        verified = None
-        if not args.no_verify:
+        result["restore_copies_in_timed_region"] = restore_in_region
+        if args.dump_outputs:  # (before --full's legs below, which sort into the same copies again)
             k, v = sets[(W + K - 1) % copies]
-            verified = verify_sorted(torch, keys0, k, v, True)
-        # roofline of the dominant kernel: the scatter pass reads key+val and writes key+val of every pair
-        passes = max(int(prof["passes"]), 1)
-        scatter_ms = prof["scatter_ms"] / passes
-        alg_bytes = n * 2 * (KEY_BYTES + VAL_BYTES)
-        achieved = alg_bytes / (scatter_ms * 1e-3) / 1e9 if scatter_ms > 0 else 0.0
-        workload_key = "radix_sort_u32_pairs_2^%d_%s_bits%d" % (log2n, args.keys, bits)
-        traffic = load_traffic(workload_key)
-        passes_per_sort = passes // K
-        # bytes the sort really moves per pair: every pass reads and writes key + val in its scatter; a pass reads the keys
-        # once more in its count kernel unless it is the second pass of a pair that took its count table from the first
-        # pass's two-digit histogram (then the pair moves that table instead: 256 x workgroups x 512 B written and read)
-        # (skipped[p]: 1 = an identity pass found by its count kernel, 2 = known before counting: no key read at all)
-        # A sort that ended in LDS (include/glu_hip.h, glu_radix_sort_read_finish): two counting passes on the top 16 key bits
-        # (one read of the keys for both tables) and one pass that orders every run of equal top bits inside LDS, reading and
-        # writing each pair once; the profile above then holds those two passes, and the in-LDS pass on its own.
-        fin = sorter.read_finish()
-        ended_in_lds = bool(fin["accepted"])
-        finish_ms = prof["finish_ms"] / max(int(prof["finish_passes"]), 1)
-        if ended_in_lds:
-            key_reads, scatters = 1, 2
-            pair_table_bytes = 2 * 256 * 256 * 512 + 2 * 65536 * 4
-            bytes_per_pair_moved = round(scatters * 2 * (KEY_BYTES + VAL_BYTES) + key_reads * KEY_BYTES + pair_table_bytes / n +
-                                         2 * (KEY_BYTES + VAL_BYTES), 2)
-        else:
-            npl = 4 if fin["attempted"] else passes_per_sort  # (the plan describes the ordinary passes)
-            skipped, alone, roles = sorter.read_plan(npl, roles=True)
-            from_table = sum(1 for p in range(npl) if roles[p] == 2 and not alone[p] and skipped[p] != 2)
-            key_reads = sum(1 for p in range(npl) if skipped[p] != 2) - from_table + (1 if fin["attempted"] else 0)
-            scatters = sum(1 for p in range(npl) if not skipped[p])
-            pair_table_bytes = sum(1 for p in range(npl) if roles[p] == 1 and skipped[p] != 2) * 2 * 256 * 256 * 512
-            bytes_per_pair_moved = round(scatters * 2 * (KEY_BYTES + VAL_BYTES) + key_reads * KEY_BYTES + pair_table_bytes / n, 2)
-        result.update({
-            "roofline": {
-                "bound": "hbm", "kernel": "radix_scatter_lines_kernel<u32,%d>" % bits,
-                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                "traffic": traffic["hbm_bytes_per_launch"] if traffic else None,
-                # not a measurement of this run: the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate runs of this
-                # same command) cannot run under the driver; the committed summary of the same workload is quoted
-                "traffic_source": ("profiles/" + traffic["_file"]) if traffic else None,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "avg_launch_ms": round(scatter_ms, 4),
-                "launches_timed": passes,
-                "count_kernel_avg_ms": round(detail["count_ms"] / max(int(detail["passes"]), 1), 4),
-                "scan_kernel_avg_ms": round(detail["scan_ms"] / max(int(detail["passes"]), 1), 4),
-                "timing": "HIP events around every scatter launch and every in-LDS pass of the timed steps (on the sort's stream); "
-                          "count / scan kernels: three more sorts after the timed region with events at every kernel boundary",
-            },
-            "whole_sort": {
-                "passes": passes_per_sort, "digit_bits": bits,
-                "count_kernels_reading_keys": key_reads, "scatter_passes_run": scatters,
-                "ended_in_lds": ended_in_lds,
-                "in_lds_pass": ({
-                    "kernel": "radix_finish_bucket_kernel", "avg_launch_ms": round(finish_ms, 4),
+            dump_outputs(torch, args.dump_outputs, k, v)
+        if args.full:  # everything below: after the timed region, on the line beside the headline
+            step_ms = sorted(a.elapsed_time(b) for a, b in step_events)
+            prof = sorter.read_profile()
+            sorter.set_profiling(False)
+            detail = {"count_ms": 0.0, "scan_ms": 0.0, "passes": 0}
+            if events:  # (outside the timed region: every kernel boundary of three more sorts)
+                sorter.set_profiling(True)
+                for i in range(W + K, W + K + 3):
+                    k, v = sets[i % copies]
+                    k.copy_(keys0)
+                    v.copy_(vals0)
+                    sorter.run_ptr(k.data_ptr(), v.data_ptr(), n, 0, stream)
+                torch.cuda.synchronize()
+                detail = sorter.read_profile()
+                sorter.set_profiling(False)
+            bits = sorter.digit_bits
+            verified = None
+            if not args.no_verify:
+                k, v = sets[(W + K - 1) % copies]
+                verified = verify_sorted(torch, keys0, k, v, True)
+            # roofline of the dominant kernel: the scatter pass reads key+val and writes key+val of every pair
+            passes = max(int(prof["passes"]), 1)
+            scatter_ms = prof["scatter_ms"] / passes
+            alg_bytes = n * 2 * (KEY_BYTES + VAL_BYTES)
+            achieved = alg_bytes / (scatter_ms * 1e-3) / 1e9 if scatter_ms > 0 else 0.0
+            workload_key = "radix_sort_u32_pairs_2^%d_%s_bits%d" % (log2n, args.keys, bits)
+            traffic = load_traffic(workload_key)
+            passes_per_sort = passes // K
+            # bytes the sort really moves per pair: every pass reads and writes key + val in its scatter; a pass reads the keys
+            # once more in its count kernel unless it is the second pass of a pair that took its count table from the first
+            # pass's two-digit histogram (then the pair moves that table instead: 256 x workgroups x 512 B written and read)
+            # (skipped[p]: 1 = an identity pass found by its count kernel, 2 = known before counting: no key read at all)
+            # A sort that ended in LDS (include/glu_hip.h, glu_radix_sort_read_finish): two counting passes on the top 16 key bits
+            # (one read of the keys for both tables) and one pass that orders every run of equal top bits inside LDS, reading and
+            # writing each pair once; the profile above then holds those two passes, and the in-LDS pass on its own.
+            fin = sorter.read_finish()
+            ended_in_lds = bool(fin["accepted"])
+            finish_ms = prof["finish_ms"] / max(int(prof["finish_passes"]), 1)
+            if ended_in_lds:
+                key_reads, scatters = 1, 2
+                pair_table_bytes = 2 * 256 * 256 * 512 + 2 * 65536 * 4
+                bytes_per_pair_moved = round(scatters * 2 * (KEY_BYTES + VAL_BYTES) + key_reads * KEY_BYTES + pair_table_bytes / n +
+                                             2 * (KEY_BYTES + VAL_BYTES), 2)
+            else:
+                npl = 4 if fin["attempted"] else passes_per_sort  # (the plan describes the ordinary passes)
+                skipped, alone, roles = sorter.read_plan(npl, roles=True)
+                from_table = sum(1 for p in range(npl) if roles[p] == 2 and not alone[p] and skipped[p] != 2)
+                key_reads = sum(1 for p in range(npl) if skipped[p] != 2) - from_table + (1 if fin["attempted"] else 0)
+                scatters = sum(1 for p in range(npl) if not skipped[p])
+                pair_table_bytes = sum(1 for p in range(npl) if roles[p] == 1 and skipped[p] != 2) * 2 * 256 * 256 * 512
+                bytes_per_pair_moved = round(scatters * 2 * (KEY_BYTES + VAL_BYTES) + key_reads * KEY_BYTES + pair_table_bytes / n, 2)
+            result.update({
+                "roofline": {
+                    "bound": "hbm", "kernel": "radix_scatter_lines_kernel<u32,%d>" % bits,
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                    "traffic": traffic["hbm_bytes_per_launch"] if traffic else None,
+                    # not a measurement of this run: the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate runs of this
+                    # same command) cannot run under the driver; the committed summary of the same workload is quoted
+                    "traffic_source": ("profiles/" + traffic["_file"]) if traffic else None,
                     "algorithmic_bytes_per_launch": alg_bytes,
-                    "achieved_GBps": round(alg_bytes / (finish_ms * 1e-3) / 1e9, 1) if finish_ms > 0 else None,
-                    "frac_of_peak": round(alg_bytes / (finish_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if finish_ms > 0 else None,
-                    "longest_run": fin["longest_run"], "capacity": fin["capacity"]} if ended_in_lds else None),
-                "bytes_per_pair_moved": bytes_per_pair_moved,
-                "achieved_GBps_own_bytes": round(units * bytes_per_pair_moved / elapsed / 1e9, 1),
-                "frac_of_peak_own_bytes": round(units * bytes_per_pair_moved / elapsed / 1e9 / HBM_PEAK_GBPS, 4),
-                # (what the reference's 8-pass structure would move, 160 B/pair, is priced in `reference_pass_structure` below,
-                # for the sort that has that structure -- not here, where it would be bytes this sort does not move)
-            },
-            "verified": verified,
-            "restore_copies_in_timed_region": restore_in_region,
-        })
-        if step_ms:
-            # the spread is the physical placement of each copy's arrays in HBM, not noise
-            result["step_device_ms"] = {"min": round(step_ms[0], 4), "median": round(step_ms[len(step_ms) // 2], 4),
-                                        "max": round(step_ms[-1], 4)}
-        # the same sort by the four ordinary passes (the attempt to end in LDS switched off), measured like the legs below:
-        # warm-ups, then steps on restored inputs, device time per sort.  Reported next to the headline, not part of `value`.
-        if ended_in_lds and not args.no_alt:
-            os.environ["GLU_HIP_SORT_LDS_FINISH"] = "0"
-            try:
-                four = G.RadixSort(digit_bits=args.digit_bits)
-            finally:
-                del os.environ["GLU_HIP_SORT_LDS_FINISH"]
-            four.prepare_internal_buffers(n)
-            f_warm, f_steps = max(W, 3), max(K, 10)
-            f_events = []
-            for i in range(f_warm + f_steps):
-                sets[i % copies][0].copy_(keys0)
-                sets[i % copies][1].copy_(vals0)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(work_stream)
-                four.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
-                e1.record(work_stream)
-                if i >= f_warm:
-                    f_events.append((e0, e1))
-            barrier()
-            f_ms = sorted(a.elapsed_time(b) for a, b in f_events)
-            f_verified = None
-            if not args.no_verify:
-                k, v = sets[(f_warm + f_steps - 1) % copies]
-                f_verified = verify_sorted(torch, keys0, k, v, True)
-            result["four_pass_sort"] = {
-                "what": "the same sort with GLU_HIP_SORT_LDS_FINISH=0: four 8-bit counting passes, 72.5 B/pair",
-                "steps": f_steps, "warmup": f_warm, "ms_per_step": round(f_ms[len(f_ms) // 2], 4), "ms_per_step_min": round(f_ms[0], 4),
-                "timing": "device time per sort (HIP events), median and min",
-                "value": round(n / (f_ms[len(f_ms) // 2] * 1e-3) / 1e6, 1), "unit": "Mkeys/s",
-                "scratch_placement": four.scratch_placement(), "verified": f_verified,
-            }
-            four.destroy()
-            del four
-        # the same sort with the reference's pass structure (8 x 4-bit digits, 160 B/pair), measured like the headline:
-        # warm-ups, then K timed steps on restored inputs (restores outside the per-step device timing), median + min.
-        # Reported next to the headline, not part of `value`.
-        if bits != 4 and not args.no_alt:
-            alt = G.RadixSort(digit_bits=4)
-            alt.prepare_internal_buffers(n)
-            alt_warm, alt_steps = max(W, 3), max(K, 10)
+                    "avg_launch_ms": round(scatter_ms, 4),
+                    "launches_timed": passes,
+                    "count_kernel_avg_ms": round(detail["count_ms"] / max(int(detail["passes"]), 1), 4),
+                    "scan_kernel_avg_ms": round(detail["scan_ms"] / max(int(detail["passes"]), 1), 4),
+                    "timing": "HIP events around every scatter launch and every in-LDS pass of the timed steps (on the sort's stream); "
+                              "count / scan kernels: three more sorts after the timed region with events at every kernel boundary",
+                },
+                "whole_sort": {
+                    "passes": passes_per_sort, "digit_bits": bits,
+                    "count_kernels_reading_keys": key_reads, "scatter_passes_run": scatters,
+                    "ended_in_lds": ended_in_lds,
+                    "in_lds_pass": ({
+                        "kernel": "radix_finish_bucket_kernel", "avg_launch_ms": round(finish_ms, 4),
+                        "algorithmic_bytes_per_launch": alg_bytes,
+                        "achieved_GBps": round(alg_bytes / (finish_ms * 1e-3) / 1e9, 1) if finish_ms > 0 else None,
+                        "frac_of_peak": round(alg_bytes / (finish_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if finish_ms > 0 else None,
+                        "longest_run": fin["longest_run"], "capacity": fin["capacity"]} if ended_in_lds else None),
+                    "bytes_per_pair_moved": bytes_per_pair_moved,
+                    "achieved_GBps_own_bytes": round(units * bytes_per_pair_moved / elapsed / 1e9, 1),
+                    "frac_of_peak_own_bytes": round(units * bytes_per_pair_moved / elapsed / 1e9 / HBM_PEAK_GBPS, 4),
+                    # (what the reference's 8-pass structure would move, 160 B/pair, is priced in `reference_pass_structure` below,
+                    # for the sort that has that structure -- not here, where it would be bytes this sort does not move)
+                },
+                "verified": verified,
+            })
+            if step_ms:
+                # the spread is the physical placement of each copy's arrays in HBM, not noise
+                result["step_device_ms"] = {"min": round(step_ms[0], 4), "median": round(step_ms[len(step_ms) // 2], 4),
+                                            "max": round(step_ms[-1], 4)}
+            # the same sort by the four ordinary passes (the attempt to end in LDS switched off), measured like the legs below:
+            # warm-ups, then steps on restored inputs, device time per sort.  Reported next to the headline, not part of `value`.
+            if ended_in_lds and not args.no_alt:
+                os.environ["GLU_HIP_SORT_LDS_FINISH"] = "0"
+                try:
+                    four = G.RadixSort(digit_bits=args.digit_bits)
+                finally:
+                    del os.environ["GLU_HIP_SORT_LDS_FINISH"]
+                four.prepare_internal_buffers(n)
+                f_warm, f_steps = max(W, 3), max(K, 10)
+                f_events = []
+                for i in range(f_warm + f_steps):
+                    sets[i % copies][0].copy_(keys0)
+                    sets[i % copies][1].copy_(vals0)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(work_stream)
+                    four.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
+                    e1.record(work_stream)
+                    if i >= f_warm:
+                        f_events.append((e0, e1))
+                barrier()
+                f_ms = sorted(a.elapsed_time(b) for a, b in f_events)
+                f_verified = None
+                if not args.no_verify:
+                    k, v = sets[(f_warm + f_steps - 1) % copies]
+                    f_verified = verify_sorted(torch, keys0, k, v, True)
+                result["four_pass_sort"] = {
+                    "what": "the same sort with GLU_HIP_SORT_LDS_FINISH=0: four 8-bit counting passes, 72.5 B/pair",
+                    "steps": f_steps, "warmup": f_warm, "ms_per_step": round(f_ms[len(f_ms) // 2], 4), "ms_per_step_min": round(f_ms[0], 4),
+                    "timing": "device time per sort (HIP events), median and min",
+                    "value": round(n / (f_ms[len(f_ms) // 2] * 1e-3) / 1e6, 1), "unit": "Mkeys/s",
+                    "scratch_placement": four.scratch_placement(), "verified": f_verified,
+                }
+                four.destroy()
+                del four
+            # the same sort with the reference's pass structure (8 x 4-bit digits, 160 B/pair), measured like the headline:
+            # warm-ups, then K timed steps on restored inputs (restores outside the per-step device timing), median + min.
+            # Reported next to the headline, not part of `value`.
+            if bits != 4 and not args.no_alt:
+                alt = G.RadixSort(digit_bits=4)
+                alt.prepare_internal_buffers(n)
+                alt_warm, alt_steps = max(W, 3), max(K, 10)
 
-            def restore(i):
-                sets[i % copies][0].copy_(keys0)
-                sets[i % copies][1].copy_(vals0)
+                def restore(i):
+                    sets[i % copies][0].copy_(keys0)
+                    sets[i % copies][1].copy_(vals0)
 
-            for i in range(alt_warm):
-                restore(i)
-                alt.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
-            barrier()
-            alt.set_profiling(True)
-            alt_events = []
-            for i in range(alt_steps):
-                restore(i)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(work_stream)
-                alt.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
-                e1.record(work_stream)
-                alt_events.append((e0, e1))
-            barrier()
-            alt_ms = sorted(a.elapsed_time(b) for a, b in alt_events)
-            ap = alt.read_profile()
-            alt.set_profiling(False)
-            alt_verified = None
-            if not args.no_verify:
-                k, v = sets[(alt_steps - 1) % copies]
-                alt_verified = verify_sorted(torch, keys0, k, v, True)
-            a_scatter_ms = ap["scatter_ms"] / max(int(ap["passes"]), 1)
-            a_med, a_min = alt_ms[len(alt_ms) // 2], alt_ms[0]
-            # bytes this sort really moved per pair (second passes of pairs that took their table from the first pass's
-            # two-digit histogram did not read the keys again; a 4-bit pair's tables are 4 MiB + 256 KiB, written and read)
-            a_passes = int(ap["passes"]) // alt_steps
-            a_skipped, a_alone, a_roles = alt.read_plan(a_passes, roles=True)
-            a_from_table = sum(1 for p in range(a_passes) if a_roles[p] == 2 and not a_alone[p] and a_skipped[p] != 2)
-            a_key_reads = sum(1 for p in range(a_passes) if a_skipped[p] != 2) - a_from_table
-            a_scatters = sum(1 for p in range(a_passes) if not a_skipped[p])
-            a_tables = sum(1 for p in range(a_passes) if a_roles[p] == 1 and a_skipped[p] != 2) * 2 * (256 * 16 * 1024 + 16 * 256 * 16 * 4)
-            a_moved = round(a_scatters * 2 * (KEY_BYTES + VAL_BYTES) + a_key_reads * KEY_BYTES + a_tables / n, 2)
-            result["reference_pass_structure"] = {
-                "digit_bits": 4, "passes": int(ap["passes"]) // alt_steps, "steps": alt_steps, "warmup": alt_warm,
-                "ms_per_step": round(a_med, 4), "ms_per_step_min": round(a_min, 4), "timing": "device time per sort (HIP events), median and min",
-                "value": round(n / (a_med * 1e-3) / 1e6, 1), "unit": "Mkeys/s",
-                "achieved_GBps_at_160B_per_pair": round(n * 160 / (a_med * 1e-3) / 1e9, 1),
-                "frac_of_peak_at_160B_per_pair": round(n * 160 / (a_med * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                "frac_of_peak_at_160B_per_pair_best": round(n * 160 / (a_min * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                "count_kernels_reading_keys": a_key_reads,
-                "bytes_per_pair_moved": a_moved,
-                "frac_of_peak_own_bytes": round(n * a_moved / (a_med * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                "scatter_kernel": "radix_scatter_lines_kernel<u32,4>",
-                "scatter_kernel_avg_ms": round(a_scatter_ms, 4),
-                "scatter_kernel_frac_of_peak": round(alg_bytes / (a_scatter_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if a_scatter_ms > 0 else None,
-                "count_kernel_avg_ms": round(ap["count_ms"] / max(int(ap["passes"]), 1), 4),
-                "verified": alt_verified,
-            }
+                for i in range(alt_warm):
+                    restore(i)
+                    alt.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
+                barrier()
+                alt.set_profiling(True)
+                alt_events = []
+                for i in range(alt_steps):
+                    restore(i)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(work_stream)
+                    alt.run_ptr(sets[i % copies][0].data_ptr(), sets[i % copies][1].data_ptr(), n, 0, stream)
+                    e1.record(work_stream)
+                    alt_events.append((e0, e1))
+                barrier()
+                alt_ms = sorted(a.elapsed_time(b) for a, b in alt_events)
+                ap = alt.read_profile()
+                alt.set_profiling(False)
+                alt_verified = None
+                if not args.no_verify:
+                    k, v = sets[(alt_steps - 1) % copies]
+                    alt_verified = verify_sorted(torch, keys0, k, v, True)
+                a_scatter_ms = ap["scatter_ms"] / max(int(ap["passes"]), 1)
+                a_med, a_min = alt_ms[len(alt_ms) // 2], alt_ms[0]
+                # bytes this sort really moved per pair (second passes of pairs that took their table from the first pass's
+                # two-digit histogram did not read the keys again; a 4-bit pair's tables are 4 MiB + 256 KiB, written and read)
+                a_passes = int(ap["passes"]) // alt_steps
+                a_skipped, a_alone, a_roles = alt.read_plan(a_passes, roles=True)
+                a_from_table = sum(1 for p in range(a_passes) if a_roles[p] == 2 and not a_alone[p] and a_skipped[p] != 2)
+                a_key_reads = sum(1 for p in range(a_passes) if a_skipped[p] != 2) - a_from_table
+                a_scatters = sum(1 for p in range(a_passes) if not a_skipped[p])
+                a_tables = sum(1 for p in range(a_passes) if a_roles[p] == 1 and a_skipped[p] != 2) * 2 * (256 * 16 * 1024 + 16 * 256 * 16 * 4)
+                a_moved = round(a_scatters * 2 * (KEY_BYTES + VAL_BYTES) + a_key_reads * KEY_BYTES + a_tables / n, 2)
+                result["reference_pass_structure"] = {
+                    "digit_bits": 4, "passes": int(ap["passes"]) // alt_steps, "steps": alt_steps, "warmup": alt_warm,
+                    "ms_per_step": round(a_med, 4), "ms_per_step_min": round(a_min, 4), "timing": "device time per sort (HIP events), median and min",
+                    "value": round(n / (a_med * 1e-3) / 1e6, 1), "unit": "Mkeys/s",
+                    "achieved_GBps_at_160B_per_pair": round(n * 160 / (a_med * 1e-3) / 1e9, 1),
+                    "frac_of_peak_at_160B_per_pair": round(n * 160 / (a_med * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                    "frac_of_peak_at_160B_per_pair_best": round(n * 160 / (a_min * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                    "count_kernels_reading_keys": a_key_reads,
+                    "bytes_per_pair_moved": a_moved,
+                    "frac_of_peak_own_bytes": round(n * a_moved / (a_med * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                    "scatter_kernel": "radix_scatter_lines_kernel<u32,4>",
+                    "scatter_kernel_avg_ms": round(a_scatter_ms, 4),
+                    "scatter_kernel_frac_of_peak": round(alg_bytes / (a_scatter_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if a_scatter_ms > 0 else None,
+                    "count_kernel_avg_ms": round(ap["count_ms"] / max(int(ap["passes"]), 1), 4),
+                    "verified": alt_verified,
+                }
         workload = "2^%d uint32 key + uint32 val pairs, %s keys, vals=iota, in-place stable radix sort, 1x MI355X" % (
             log2n, "uniform-random full-range" if args.keys == "uniform" else "all-zero")
         parallelism = "single"
@@ -693,6 +745,8 @@ def main():
             if args.rehearse_one_gpu:
                 res["rehearsal"] = "NOT A MEASUREMENT: %d ranks share one GPU and exchange through files (tests/cpp/mock_rccl.cpp)" % world
             rk, rv, cnt = handle.synchronize()
+            if args.dump_outputs and rank == 0 and native == want_native:  # (the run whose line is printed: rank 0's shard)
+                dump_outputs(torch, args.dump_outputs, rk[:cnt], rv[:cnt])
             # rank 0's view: the scatter kernel (1 partition launch over n pairs + 4 sort launches over its shard per sort)
             # and the device time of every phase of a sort
             launches = sum(int(pf["passes"]) for pf in profs)
@@ -849,7 +903,7 @@ def main():
 
     if rank == 0:
         line = make_line(result, elapsed, units, workload, parallelism)
-        if world == 1 and not args.force_dist and not args.no_cpu_baseline:
+        if world == 1 and not args.force_dist and args.full and not args.no_cpu_baseline:
             if args.cpu_sample_log2 is None:
                 # the same input array as the GPU sorted, whole, one run per configuration
                 kh = keys0.cpu().numpy().view("uint32")

@@ -56,3 +56,40 @@ def test_pair_fingerprint_is_a_multiset_check_of_key_value_pairs():
     v2[0], v2[1] = v[1], v[0]  # ... two pairs of different keys do not
     assert not bool((bench.pair_fingerprint(torch, k, v2) == a).all())
     assert not bool((bench.pair_fingerprint(torch, k[1:], v[1:]) == a).all())
+
+
+def test_dump_outputs_writes_a_seeded_sample_and_block_sums(tmp_path):
+    """--dump-outputs: float64 files of the caller's sorted pairs, read as unsigned 32-bit values; the sampled positions are
+    the same from run to run, the block sums cover every element, and the whole dump stays under 64 MB at the headline size."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_SAMPLE * 2 + 5
+    g = torch.Generator().manual_seed(5)
+    keys = torch.randint(-2**31, 2**31, (n,), dtype=torch.int32, generator=g)
+    vals = torch.arange(n, dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), keys, vals)
+    names = ["keys", "values", "keys_block_sums", "values_block_sums"]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(m + ".npy" for m in names)
+    for m in names:
+        a, b = np.load(tmp_path / "a" / (m + ".npy")), np.load(tmp_path / "b" / (m + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b), m
+    uk = keys.numpy().view(np.uint32).astype(np.float64)
+    k = np.load(tmp_path / "a" / "keys.npy")
+    v = np.load(tmp_path / "a" / "values.npy").astype(np.int64)
+    assert bench.DUMP_SAMPLE // 2 < len(k) <= bench.DUMP_SAMPLE + 2 and v[0] == 0 and v[-1] == n - 1
+    assert np.array_equal(k, uk[v])  # (vals = iota: each sampled value is its own position)
+    sums = np.load(tmp_path / "a" / "keys_block_sums.npy")
+    assert len(sums) == bench.DUMP_BLOCKS and sums.astype(np.int64).sum() == uk.astype(np.int64).sum()
+    assert np.load(tmp_path / "a" / "values_block_sums.npy").sum() == n * (n - 1) // 2
+    # the largest the dump can get (every sampled position distinct) is 2 x (DUMP_SAMPLE + 2) + 2 x DUMP_BLOCKS float64 values
+    assert (2 * (bench.DUMP_SAMPLE + 2) + 2 * bench.DUMP_BLOCKS) * 8 < 64e6
+    # small outputs are written whole
+    bench.dump_outputs(torch, str(tmp_path / "c"), keys[:1000], vals[:1000])
+    assert np.array_equal(np.load(tmp_path / "c" / "keys.npy"), uk[:1000])

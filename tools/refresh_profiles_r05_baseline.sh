@@ -15,5 +15,5 @@ python tools/trace_summary.py $(find $OUT/prof_c5 -name "*kernel_trace.csv" | he
 find $OUT/prof_c5 -name "*kernel_stats.csv" -exec cp {} $OUT/c5_kernel_stats_baseline.csv \;
 rm -rf $OUT/prof_c5
 python tools/sort_loop.py --log2 28 --key-bytes 8 > $OUT/c5_loop_baseline.txt 2>&1
-python bench.py --no-cpu-baseline > $OUT/bench_n1_baseline.json 2> $OUT/bench_n1_baseline.err
+python bench.py --full --no-cpu-baseline > $OUT/bench_n1_baseline.json 2> $OUT/bench_n1_baseline.err
 ls -la $OUT
