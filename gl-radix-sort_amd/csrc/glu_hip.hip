@@ -95,6 +95,13 @@ glu_status sort_prepare(glu_radix_sort_s* s, size_t count, size_t key_size, bool
 }
 
 
+} // namespace
+glu_status glu_hip::host::sort_prepare_plain(glu_radix_sort_s* s, size_t count, size_t key_size, bool with_vals)
+{
+    return sort_prepare(s, count, key_size, with_vals, false);
+}
+namespace
+{
 // n <= one tile: the whole sort in a single workgroup / single launch (always 8-bit digits: the result does not
 // depend on the digit width)
 template<typename KeyT, int THREADS, int KPT, bool XF>
@@ -1161,6 +1168,23 @@ const SortOption kSortOptions[] = {
 #undef GLU_OPT
 }
 
+// The ordinary typed sort as a linear chain on `stream`.  The sort's only fork is the side stream of a sort that tries to end in LDS
+// (sort_bits: `fork`, switched by glu_radix_sort_s::fork_behind); whatever else is ever moved off the caller's queue has to ask
+// fork_behind too, or this function's promise breaks.
+glu_status glu_hip::host::sort_typed_one_queue(glu_radix_sort_s* s, void* keys, uint32_t* vals, size_t count, glu_key_type key_type,
+                                               hipStream_t stream)
+{
+    const bool fork = s->fork_behind;
+    s->fork_behind = false;
+    const uint32_t xf = (key_type == GLU_KEY_INT32 || key_type == GLU_KEY_INT64)       ? KEY_XF_SIGNED
+                        : (key_type == GLU_KEY_FLOAT32 || key_type == GLU_KEY_FLOAT64) ? KEY_XF_FLOAT
+                                                                                       : KEY_XF_NONE;
+    const glu_status status = (int) key_type >= (int) GLU_KEY_UINT64 ? sort_run<uint64_t>(s, (uint64_t*) keys, vals, count, 0, stream, xf)
+                                                                     : sort_run<uint32_t>(s, (uint32_t*) keys, vals, count, 0, stream, xf);
+    s->fork_behind = fork;
+    return status;
+}
+
 extern "C" {
 
 glu_status glu_radix_sort_create(glu_radix_sort* out)
@@ -1188,7 +1212,7 @@ glu_status glu_radix_sort_destroy(glu_radix_sort sort)
     // library queue, before its scratch goes away (RAII of the reference: RadixSort.hpp:194-200, gl_utils.hpp:184-188)
     (void) hipDeviceSynchronize();
     for (Scratch* sc : {&sort->keys, &sort->vals, &sort->table, &sort->plan, &sort->pair_t2, &sort->pair_table, &sort->pair_ranges,
-                        &sort->pair_sub, &sort->pair_wide, &sort->seg_desc, &sort->seg_zero, &sort->finish_lengths, &sort->finish_starts, &sort->finish_crowded, &sort->finish_outcomes, &sort->seg_gate, &sort->long_image, &sort->long_hdr, &sort->long_bits})
+                        &sort->pair_sub, &sort->pair_wide, &sort->seg_desc, &sort->seg_zero, &sort->finish_lengths, &sort->finish_starts, &sort->finish_crowded, &sort->finish_outcomes, &sort->seg_gate, &sort->long_image, &sort->long_hdr, &sort->long_bits, &sort->batch_lists})
         sc->release();
     if (sort->finish_hint) (void) hipHostFree(sort->finish_hint);
     for (hipEvent_t e : {sort->ev_fork, sort->ev_unit, sort->ev_fork2, sort->ev_join})
@@ -1695,7 +1719,7 @@ glu_status glu_radix_sort_scratch_size(glu_radix_sort sort, size_t* bytes)
     if (!sort || !bytes) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
     *bytes = sort->keys.size + sort->vals.size + sort->table.size + sort->plan.size + sort->pair_t2.size + sort->pair_table.size +
              sort->pair_ranges.size + sort->pair_sub.size + sort->seg_desc.size + sort->seg_zero.size + sort->finish_lengths.size +
-             sort->finish_starts.size + sort->seg_gate.size + sort->long_image.size + sort->long_hdr.size;
+             sort->finish_starts.size + sort->seg_gate.size + sort->long_image.size + sort->long_hdr.size + sort->batch_lists.size;
     return GLU_OK;
 }
 

@@ -111,6 +111,10 @@ struct glu_radix_sort_s
     Scratch seg_desc;    // segmented passes (glu_dist's local sort): sub-block descriptors of the pass being enqueued
     Scratch seg_zero;    // and RADIX zero words (the digit totals a segmented scatter adds to its absolute table entries)
     bool last_planned = false; // the last sort on this object ran with a device-side plan (glu_radix_sort_read_plan)
+    // the batched sort (glu_sort_batch.hip): the list counts and the five lists of segment indices its binning kernel writes
+    Scratch batch_lists;
+    uint32_t last_batch[3] = {};       // segments per class (wave, workgroup, long) of the last batched call, where the host chose
+    bool last_batch_on_device = false; // ... the device did: glu_radix_sort_read_batch reads the list counts
     // pinned host images of the descriptors, a ring: a call fills the next one and enqueues its copy; an image is reused
     // only after the copy enqueued from it has run (its event)
     struct SegStage
@@ -338,6 +342,13 @@ bool lines_applicable(const glu_radix_sort_s* s, const void* src_k, const void* 
     // (at least one whole tile: the kernel's branch-free prefetch reads tile 0 when it has nothing better to read)
     return aligned && !s->no_lines && !s->force_small && count >= lines_tile && count >= large_tiles_from<KeyT, BITS>(s, vals, lines_tile);
 }
+
+// The lazy scratch allocation at the head of a sort (glu_hip.hip: sort_prepare without the placement search), for the batched sort's
+// translation unit.
+glu_status sort_prepare_plain(glu_radix_sort_s* s, size_t count, size_t key_size, bool with_vals);
+// glu_radix_sort_run_typed_ptr's sort with every launch on `stream` itself: no part of the launch sequence may go to the object's side
+// stream (glu_hip.hip, beside the one place that forks).  The batched sort loops it over partitions longer than an LDS tile.
+glu_status sort_typed_one_queue(glu_radix_sort_s* s, void* keys, uint32_t* vals, size_t count, glu_key_type key_type, hipStream_t stream);
 
 // One counting pass (count -> row scan -> scatter, or the leader / follower of a pair of passes), 4- or 8-bit digits, the geometry
 // by size: glu_sort_passes.hpp, instantiated for 4-byte keys in glu_sort_passes_u32.hip and for 8-byte keys in _u64.hip.

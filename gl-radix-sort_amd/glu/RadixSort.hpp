@@ -73,6 +73,41 @@ namespace glu
                                                               begin_bit, end_bit, stream));
         }
 
+        /// Batched sort (not in the reference; glu_radix_sort_run_batch_ptr in glu_hip.h): `num_partitions` adjacent partitions of
+        /// `count` elements each -- the shape of BlellochScan::operator() -- every one sorted on its own, stable, ascending, in
+        /// place, in one asynchronous launch sequence.  KeyT as in sort_typed; device_vals may be nullptr (keys only).
+        template<typename KeyT>
+        void sort_batch(KeyT* device_keys, uint32_t* device_vals, size_t count, size_t num_partitions, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_radix_sort_run_batch_ptr(m_impl, device_keys, device_vals, count, num_partitions, key_type_of<KeyT>(), stream));
+        }
+        /// The same for segments of any lengths: segment s = elements [offsets[s], offsets[s + 1]) of the arrays of `total`
+        /// elements; device_offsets is a DEVICE array of num_segments + 1 non-decreasing uint32 and is not read by the host.
+        template<typename KeyT>
+        void sort_batch_offsets(KeyT* device_keys, uint32_t* device_vals, size_t total, const uint32_t* device_offsets,
+                                size_t num_segments, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_radix_sort_run_batch_offsets_ptr(m_impl, device_keys, device_vals, total, device_offsets, num_segments,
+                                                                  key_type_of<KeyT>(), stream));
+        }
+        /// Scratch for batched sorts of up to `total` elements in up to `num_segments` segments (they then allocate nothing and can be
+        /// captured into a graph).
+        void prepare_internal_buffers_batch(size_t total, size_t num_segments, size_t key_bytes = 4, bool with_vals = true)
+        {
+            GLU_CHECK_STATUS(glu_radix_sort_prepare_batch(m_impl, total, num_segments, key_bytes, with_vals ? 1 : 0));
+        }
+        /// Segments each path of the last batched call took (glu_radix_sort_read_batch; synchronise its stream first).
+        struct BatchReport
+        {
+            uint32_t wave_segments = 0, block_segments = 0, long_segments = 0;
+        };
+        [[nodiscard]] BatchReport last_batch() const
+        {
+            BatchReport r;
+            GLU_CHECK_STATUS(glu_radix_sort_read_batch(m_impl, &r.wave_segments, &r.block_segments, &r.long_segments));
+            return r;
+        }
+
         /// One piece of the input of sort_segments: elements [begin, begin + length) of the input arrays, part of `segment`.
         struct Piece
         {

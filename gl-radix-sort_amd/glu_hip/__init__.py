@@ -77,6 +77,11 @@ SYMBOLS = [
     ("glu_radix_sort_read_finish", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_radix_sort_read_long_runs", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_radix_sort_read_seg_finish", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_radix_sort_run_batch_ptr", _int, [_vp, _vp, _vp, _sz, _sz, _int, _vp]),
+    ("glu_radix_sort_run_batch_offsets_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _sz, _int, _vp]),
+    ("glu_radix_sort_prepare_batch", _int, [_vp, _sz, _sz, _sz, _int]),
+    ("glu_radix_sort_plan_batch", _int, [_sz, _u32, _int, _P(_u32), _P(_u32)]),
+    ("glu_radix_sort_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_scan_create", _int, [_int, _P(_vp)]),
     ("glu_scan_destroy", _int, [_vp]),
     ("glu_scan_prepare", _int, [_vp, _sz, _sz]),
@@ -248,6 +253,14 @@ def plan_finish(count, key_bytes=4):
     return a.value, b.value
 
 
+def plan_batch(count, key_bytes=4, with_vals=True):
+    """(path, tile) of a batch of equal partitions of `count` elements (glu_radix_sort_plan_batch; host only): path 0 = nothing to
+    do, 1 = a wave per partition, 2 = a workgroup per partition, 3 = longer than an LDS tile; tile in elements."""
+    a, b = _u32(0), _u32(0)
+    check(lib().glu_radix_sort_plan_batch(count, key_bytes, 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
 class RadixSort:
     """glu::RadixSort (reference glu/RadixSort.hpp:186-354) over the C ABI."""
 
@@ -356,6 +369,29 @@ class RadixSort:
         """key_type: a numpy dtype name in KEY_TYPES; vals_ptr may be None (keys only)."""
         check(lib().glu_radix_sort_run_typed_ptr(self._h, _vp(keys_ptr), _vp(vals_ptr), count, self.KEY_TYPES[key_type],
                                                  _vp(stream)))
+
+    def sort_batch_ptr(self, keys_ptr, vals_ptr, count, num_partitions, key_type="uint32", stream=None):
+        """Batched sort: num_partitions adjacent partitions of `count` elements, each sorted on its own, in place
+        (glu_radix_sort_run_batch_ptr); vals_ptr may be None (keys only)."""
+        check(lib().glu_radix_sort_run_batch_ptr(self._h, _vp(keys_ptr), _vp(vals_ptr), count, num_partitions,
+                                                 self.KEY_TYPES[key_type], _vp(stream)))
+
+    def sort_batch_offsets_ptr(self, keys_ptr, vals_ptr, total, offsets_ptr, num_segments, key_type="uint32", stream=None):
+        """Batched sort of the segments [offsets[s], offsets[s + 1]) -- offsets_ptr: DEVICE array of num_segments + 1 uint32 --
+        each on its own, in place (glu_radix_sort_run_batch_offsets_ptr); vals_ptr may be None (keys only)."""
+        check(lib().glu_radix_sort_run_batch_offsets_ptr(self._h, _vp(keys_ptr), _vp(vals_ptr), total, _vp(offsets_ptr),
+                                                         num_segments, self.KEY_TYPES[key_type], _vp(stream)))
+
+    def prepare_batch(self, total, num_segments, key_bytes=4, with_vals=True):
+        """Grow-only scratch for batched sorts of up to `total` elements in up to `num_segments` segments: after it the two
+        calls above allocate nothing (glu_radix_sort_prepare_batch)."""
+        check(lib().glu_radix_sort_prepare_batch(self._h, total, num_segments, key_bytes, 1 if with_vals else 0))
+
+    def read_batch(self):
+        """{wave, block, long}: segments each path of the last batched call took (glu_radix_sort_read_batch); synchronise first."""
+        a, b, c = _u32(0), _u32(0), _u32(0)
+        check(lib().glu_radix_sort_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"wave": a.value, "block": b.value, "long": c.value}
 
     def sort_bit_range_ptr(self, keys_ptr, vals_ptr, count, begin_bit, end_bit, stream=None, key_bytes=4):
         """Stable sort by the key bits [begin_bit, end_bit) only; vals_ptr may be None (keys only)."""

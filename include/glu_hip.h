@@ -334,6 +334,51 @@ GLU_API glu_status glu_radix_sort_read_seg_finish(glu_radix_sort sort, uint32_t*
                                                   uint32_t* longest_run, uint32_t* capacity, uint32_t* runs, uint32_t* tile,
                                                   uint32_t* split);
 
+/* ---- batched radix sort (not in the reference, whose RadixSort sorts one array per call while its BlellochScan takes
+ * num_partitions, glu/BlellochScan.hpp:130-139): a stable ascending sort of EVERY SEGMENT of an array independently, in place,
+ * in one asynchronous launch sequence, for all six glu_key_type's, with a uint32 value array or without (vals == NULL: keys only).
+ *   - Result per segment = the stable sort glu_radix_sort_run_typed_ptr gives for that slice alone (the same natural order of
+ *     signed and float keys: -0 < +0, NaNs beyond the infinities of their sign); values follow their keys.
+ *   - Elements outside [offsets[0], offsets[num_segments]) are not touched.  Empty segments and segments of one element are legal.
+ *     total, and count * num_partitions, must be < 2^32; num_segments (num_partitions) <= 2^24.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check: NULL keys with a non-zero size, an array that is not aligned to its
+ *     element size, an unknown key type, count * num_partitions beyond the limit.  `offsets` lives on the DEVICE and is not read by
+ *     the host: the kernels treat a segment whose end is below its begin, or beyond `total`, as empty, and so never reach outside
+ *     [0, total); which elements move is then unspecified.  Offsets must be non-decreasing for the result above.
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back of `offsets`, no side stream (a captured graph is a
+ *     linear chain), and no device allocation once glu_radix_sort_prepare_batch covered the sizes (else grow-only allocation inside
+ *     the call, as in every other entry point: not capturable).
+ *   - Three size classes.  Up to 512 elements a WAVE sorts the segment (registers + a wave-private LDS slice, no workgroup barrier:
+ *     the waves of a workgroup work on different segments); up to the single-block limit (16384 elements with 4-byte keys, 8192
+ *     with 8-byte keys) a WORKGROUP sorts it inside LDS, in a tile of 1024, 4096 or 16384 (8192) elements; both read and write
+ *     every element once.  LONGER segments: with device offsets one workgroup per segment streams 8-bit counting passes between the
+ *     caller's arrays and the object's scratch arrays (correct for any length, one CU per segment: meant for the few long segments
+ *     of a mixed batch); equal partitions longer than a tile are sorted one after the other by the ordinary sort, each large
+ *     enough to fill the device.  With device offsets a binning kernel lists the segments of every class first and every class
+ *     kernel walks its list with a grid sized to the device: seven launches whatever the segments look like. */
+
+/* num_partitions adjacent partitions of `count` elements each (the shape of glu_scan_run_ptr) */
+GLU_API glu_status glu_radix_sort_run_batch_ptr(glu_radix_sort sort, void* keys, uint32_t* vals, size_t count,
+                                                size_t num_partitions, glu_key_type key_type, void* stream);
+/* segment s = elements [offsets[s], offsets[s+1]); offsets: DEVICE array of num_segments + 1 uint32, non-decreasing */
+GLU_API glu_status glu_radix_sort_run_batch_offsets_ptr(glu_radix_sort sort, void* keys, uint32_t* vals, size_t total,
+                                                        const uint32_t* offsets, size_t num_segments,
+                                                        glu_key_type key_type, void* stream);
+/* Grow-only scratch so that the two calls above allocate nothing (and can be captured) for batches of up to `total` elements of
+ * `key_bytes`-byte keys (4 or 8) in up to `num_segments` segments: the segment lists (at most 4 bytes per segment and class that
+ * fits `total`) and, for the long class and for equal partitions beyond a tile, key (+ value) scratch of `total` elements
+ * (glu_radix_sort_prepare_ex, with what it says about placing large arrays). */
+GLU_API glu_status glu_radix_sort_prepare_batch(glu_radix_sort sort, size_t total, size_t num_segments, size_t key_bytes,
+                                                int with_vals);
+/* Host only, no device (unit-testable, like glu_radix_sort_plan_finish): which path an equal-length batch takes and the tile
+ * it uses: path 0 = nothing to do (count <= 1), 1 = wave per segment, 2 = workgroup per segment, 3 = longer than an LDS tile
+ * (tile: the largest one); tile in elements.  Either pointer may be NULL. */
+GLU_API glu_status glu_radix_sort_plan_batch(size_t count, uint32_t key_bytes, int with_vals, uint32_t* path, uint32_t* tile);
+/* Diagnostics of the last batched call on the object (the caller has synchronised its stream): how many segments each path took
+ * (segments of 0 or 1 elements take none).  Any pointer may be NULL. */
+GLU_API glu_status glu_radix_sort_read_batch(glu_radix_sort sort, uint32_t* wave_segments, uint32_t* block_segments,
+                                             uint32_t* long_segments);
+
 /* ---- exclusive scan: replaces glu::BlellochScan (glu/BlellochScan.hpp:80-191) ---------------------- */
 
 /* BlellochScan::BlellochScan(data_type)                (BlellochScan.hpp:91-121) */
