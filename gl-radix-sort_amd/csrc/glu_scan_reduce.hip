@@ -5,50 +5,11 @@
 #include <vector>
 
 #include "glu_host.hpp"
+#include "glu_reduce_object.hpp"
 #include "scan_reduce_kernels.hpp"
 
 using namespace glu_hip;
 using namespace glu_hip::host;
-
-// ------------------------------------------------------------------------------------------------------------
-// scan / reduce: data-type dispatch
-// ------------------------------------------------------------------------------------------------------------
-namespace
-{
-size_t data_type_size(glu_data_type t)
-{
-    switch (t)
-    {
-    case GLU_DATA_TYPE_FLOAT: case GLU_DATA_TYPE_INT: case GLU_DATA_TYPE_UINT: return 4;
-    case GLU_DATA_TYPE_DOUBLE: case GLU_DATA_TYPE_VEC2: case GLU_DATA_TYPE_UVEC2: case GLU_DATA_TYPE_IVEC2: return 8;
-    case GLU_DATA_TYPE_VEC4: case GLU_DATA_TYPE_UVEC4: case GLU_DATA_TYPE_IVEC4: case GLU_DATA_TYPE_DVEC2: return 16;
-    case GLU_DATA_TYPE_DVEC4: return 32;
-    default: return 0;
-    }
-}
-
-// calls f.template operator()<S, N>() for the scalar type / component count of `t`
-template<typename F>
-glu_status dispatch_type(glu_data_type t, F&& f)
-{
-    switch (t)
-    {
-    case GLU_DATA_TYPE_FLOAT: return f.template operator()<float, 1>();
-    case GLU_DATA_TYPE_DOUBLE: return f.template operator()<double, 1>();
-    case GLU_DATA_TYPE_INT: return f.template operator()<int32_t, 1>();
-    case GLU_DATA_TYPE_UINT: return f.template operator()<uint32_t, 1>();
-    case GLU_DATA_TYPE_VEC2: return f.template operator()<float, 2>();
-    case GLU_DATA_TYPE_VEC4: return f.template operator()<float, 4>();
-    case GLU_DATA_TYPE_DVEC2: return f.template operator()<double, 2>();
-    case GLU_DATA_TYPE_DVEC4: return f.template operator()<double, 4>();
-    case GLU_DATA_TYPE_UVEC2: return f.template operator()<uint32_t, 2>();
-    case GLU_DATA_TYPE_UVEC4: return f.template operator()<uint32_t, 4>();
-    case GLU_DATA_TYPE_IVEC2: return f.template operator()<int32_t, 2>();
-    case GLU_DATA_TYPE_IVEC4: return f.template operator()<int32_t, 4>();
-    default: return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data type: %d", (int) t);
-    }
-}
-} // namespace
 
 struct glu_scan_s
 {
@@ -60,13 +21,6 @@ struct glu_scan_s
     uint32_t epoch = 0;
     bool chained = true; // GLU_HIP_SCAN_CHAINED=0 falls back to reduce-then-scan
     size_t chain_min_chunks = kChainMinChunks; // GLU_HIP_SCAN_CHAINED=2: chained from 2 chunks up (tests)
-};
-
-struct glu_reduce_s
-{
-    glu_data_type type;
-    glu_reduce_operator op;
-    Scratch partials;
 };
 
 namespace
@@ -361,6 +315,8 @@ glu_status glu_reduce_destroy(glu_reduce reduce)
     if (!reduce) return GLU_OK;
     (void) hipDeviceSynchronize();
     reduce->partials.release();
+    reduce->batch_lists.release();
+    reduce->batch_partials.release();
     delete reduce;
     return GLU_OK;
 }

@@ -1,0 +1,404 @@
+// reduce_batch_kernels.hpp -- gfx950 kernels of the BATCHED reduce (glu_reduce_run_batch_ptr / _batch_offsets_ptr): every segment of
+// an array folded on its own, out[s] = op over the segment, the input left alone.  Not in the reference, whose Reduce folds one
+// array per call into its element 0 (glu/Reduce.hpp:111-135).
+//
+// Three size classes (reduce_batch_plan is the one place that draws the lines, in BYTES of a segment):
+//   short   reduce_batch_wave_kernel    up to 4 KiB: a group of 4 / 16 / 64 lanes of a wave folds one segment (up to 16, up to 64,
+//                                       more elements), so a wave holds 16 / 4 / 1 segments and no lane idles on 32-element
+//                                       segments.  Scalar loads, four in flight per lane, shuffles inside the group, no LDS, no
+//                                       barrier, one store per segment.
+//   medium  reduce_batch_block_kernel   up to 256 KiB: a workgroup folds one segment with 16-byte loads from the segment's first
+//                                       16-byte-aligned element, the few elements before and behind it one per lane.
+//   long    reduce_batch_chunk_kernel   the segment is cut into chunks of 256 KiB, a workgroup folds one chunk into
+//                                       partials[its slot]; reduce_batch_block_kernel in COMBINE mode then folds every long
+//                                       segment's partials, which lie side by side in chunk order.
+// reduce_batch_bin_kernel in front (device offsets only) writes the identity of empty segments and the lists: three short lists,
+// the medium list, the long list and the list of chunks.  A segment is [offsets[s], offsets[s + 1]); one whose end lies below its
+// begin or beyond `total` is EMPTY to every kernel here (reduce_batch_segment), so nothing outside [0, total) is ever read.
+//
+// Order of combination: a lane folds its elements in ascending order, groups / waves / workgroups combine in lane, wave and chunk
+// order.  Which element goes to which lane depends on the segment's address (the 16-byte alignment), its length and nothing else:
+// no atomics on values, nothing in arrival order (list positions are, but every item writes a slot of its own and the slots of one
+// segment are adjacent and ordered).  No identity is needed inside the folds (the `has` flags of block_reduce).
+#pragma once
+
+#include "scan_reduce_kernels.hpp"
+
+namespace glu_hip
+{
+constexpr uint32_t kRbWaveBytes = 4096;         // longest segment of the short class
+constexpr uint32_t kRbBlockBytes = 256 * 1024;  // longest segment of the medium class
+constexpr uint32_t kRbChunkBytes = 256 * 1024;  // chunk of the long class
+constexpr uint32_t kRbGroup4Elems = 16;         // up to here 4 lanes fold a segment
+constexpr uint32_t kRbGroup16Elems = 64;        // up to here 16 lanes, beyond it the whole wave
+constexpr int kRbThreads = 256;
+constexpr int kRbWaves = kRbThreads / kW;
+constexpr int kRbUnroll = 4;                    // loads in flight per lane
+
+enum
+{
+    RB_LIST_SHORT4 = 0,
+    RB_LIST_SHORT16 = 1,
+    RB_LIST_SHORT64 = 2,
+    RB_LIST_BLOCK = 3,
+    RB_LIST_LONG = 4,   // uint2 entries: segment, slot of its first chunk
+    RB_LIST_CHUNKS = 5, // uint2 entries: segment, chunk of the segment
+    RB_LISTS = 6
+};
+// counts[0 .. 3]: lengths of the four segment lists; counts[4 .. 5]: chunk slots handed out, ONE 64-bit counter (overlapping long
+// segments -- malformed offsets only -- can ask for far more than 2^32 of them, and it must not wrap); counts[6]: long segments.
+constexpr int kRbCountChunks = 4, kRbCountLong = 6, kRbCounts = 7;
+
+// host only: class (0 = empty, 1 = short, 2 = medium, 3 = long) and workgroups one segment of `count` elements is spread over
+inline void reduce_batch_plan(uint64_t count, uint32_t elem_bytes, uint32_t& path, uint32_t& workgroups)
+{
+    workgroups = count ? 1u : 0u;
+    if (count == 0) path = 0;
+    else if (count <= kRbWaveBytes / elem_bytes) path = 1;
+    else if (count <= kRbBlockBytes / elem_bytes) path = 2;
+    else
+    {
+        path = 3;
+        const uint64_t chunk = kRbChunkBytes / elem_bytes;
+        const uint64_t n = (count + chunk - 1) / chunk;
+        workgroups = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t) n;
+    }
+}
+
+struct ReduceBatchLayout
+{
+    uint32_t start[RB_LISTS];    // first word of list c behind the counts
+    uint32_t capacity[RB_LISTS]; // entries list c holds
+    uint32_t limit[4];           // longest segment (elements) of the four segment lists; longer ones are long
+    uint32_t chunk;              // elements of a chunk
+};
+
+struct ReduceBatchArgs
+{
+    const uint32_t* offsets; // device offsets, or NULL: equal partitions of `count` elements
+    uint64_t count;
+    uint32_t total;          // device offsets: elements of the array
+    uint32_t nsegs;          // segments / partitions
+    uint32_t chunks_per;     // equal partitions of the long class: chunks of one partition
+    int sub;                 // equal partitions of the short class: which group size (RB_LIST_SHORT*)
+    const uint32_t* counts;  // device offsets: the list counts and the lists
+    const uint32_t* lists;
+    ReduceBatchLayout layout;
+};
+
+struct ReduceBatchIdentity
+{
+    uint32_t w[8]; // the operator's identity element, as the words of one element
+};
+
+// Element range of segment `seg` (see the head of the file for malformed offsets).
+__device__ __forceinline__ void reduce_batch_segment(const ReduceBatchArgs& a, uint32_t seg, uint64_t& begin, uint64_t& len)
+{
+    if (a.offsets)
+    {
+        const uint32_t b = a.offsets[seg];
+        uint32_t e = a.offsets[seg + 1];
+        if (e < b || e > a.total) e = b;
+        begin = b;
+        len = e - b;
+    }
+    else
+    {
+        begin = (uint64_t) seg * a.count;
+        len = a.count;
+    }
+}
+
+// entries of list c a kernel walks: what the binning kernel counted, never more than the list holds
+__device__ __forceinline__ uint32_t reduce_batch_list_length(const ReduceBatchArgs& a, int c)
+{
+    const uint64_t n = c == RB_LIST_CHUNKS ? *reinterpret_cast<const unsigned long long*>(a.counts + kRbCountChunks)
+                                           : (uint64_t) a.counts[c == RB_LIST_LONG ? kRbCountLong : c];
+    return n < a.layout.capacity[c] ? (uint32_t) n : a.layout.capacity[c];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Binning (device offsets).  Empty segments get the identity here; every other segment is appended to the list of its class
+// (wave-aggregated: one atomic per wave and list), a long one also with one entry per chunk, written by the whole wave.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatchArgs a, uint32_t* __restrict__ counts, uint32_t* __restrict__ lists,
+                                                               uint32_t* __restrict__ out, uint32_t elem_words, ReduceBatchIdentity identity)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t base = blockIdx.x * 256u; base < a.nsegs; base += gridDim.x * 256u)
+    {
+        const uint32_t seg = base + threadIdx.x;
+        int cls = -1;
+        uint32_t nchunks = 0;
+        if (seg < a.nsegs)
+        {
+            uint64_t begin, len;
+            reduce_batch_segment(a, seg, begin, len);
+            if (len == 0)
+            {
+                for (uint32_t w = 0; w < elem_words; w++) out[(size_t) seg * elem_words + w] = identity.w[w];
+            }
+            else
+            {
+                cls = RB_LIST_LONG;
+#pragma unroll
+                for (int c = RB_LIST_BLOCK; c >= 0; c--)
+                    if (len <= a.layout.limit[c]) cls = c;
+                if (cls == RB_LIST_LONG) nchunks = (uint32_t) ((len + a.layout.chunk - 1) / a.layout.chunk);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c <= RB_LIST_BLOCK; c++)
+        {
+            const uint64_t m = __ballot(cls == c);
+            if (m == 0) continue; // wave-uniform
+            const int leader = __ffsll((unsigned long long) m) - 1;
+            uint32_t first = 0;
+            if ((int) lane == leader) first = atomicAdd(&counts[c], (uint32_t) __popcll(m));
+            first = (uint32_t) __shfl((int) first, leader);
+            if (cls == c)
+            {
+                const uint32_t at = first + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
+                if (at < a.layout.capacity[c]) lists[a.layout.start[c] + at] = seg; // (cannot overflow with non-decreasing offsets)
+            }
+        }
+        // Long segments are few (each is longer than a chunk): atomics of its own for each.  First its run of chunk slots; its
+        // place in the long list only if the whole run lies inside the chunk list, so that every listed segment has all its
+        // partials.  (Non-decreasing offsets always fit; of overlapping segments those that do not get no result.)
+        uint32_t slot = a.layout.capacity[RB_LIST_CHUNKS];
+        if (cls == RB_LIST_LONG)
+        {
+            const unsigned long long got = atomicAdd(reinterpret_cast<unsigned long long*>(counts + kRbCountChunks), (unsigned long long) nchunks);
+            if (got < a.layout.capacity[RB_LIST_CHUNKS]) slot = (uint32_t) got;
+            if (got + nchunks <= a.layout.capacity[RB_LIST_CHUNKS])
+            {
+                const uint32_t at = atomicAdd(&counts[kRbCountLong], 1u);
+                if (at < a.layout.capacity[RB_LIST_LONG])
+                {
+                    uint2* entry = reinterpret_cast<uint2*>(lists + a.layout.start[RB_LIST_LONG]) + at;
+                    *entry = make_uint2(seg, slot);
+                }
+            }
+        }
+        // every slot below the chunk list's length gets its entry, also from a run that only begins inside the list
+        uint64_t m = __ballot(cls == RB_LIST_LONG);
+        while (m) // wave-uniform
+        {
+            const int src = __ffsll((unsigned long long) m) - 1;
+            m &= m - 1;
+            const uint32_t s_seg = (uint32_t) __shfl((int) seg, src);
+            const uint32_t s_slot = (uint32_t) __shfl((int) slot, src);
+            const uint32_t s_n = (uint32_t) __shfl((int) nchunks, src);
+            uint2* chunks = reinterpret_cast<uint2*>(lists + a.layout.start[RB_LIST_CHUNKS]);
+            for (uint32_t c = lane; c < s_n; c += kW)
+                if ((uint64_t) s_slot + c < a.layout.capacity[RB_LIST_CHUNKS]) chunks[s_slot + c] = make_uint2(s_seg, c);
+        }
+    }
+}
+
+// out[s] = identity for s < n (equal partitions of no elements)
+__global__ __launch_bounds__(256) void reduce_batch_fill_kernel(uint32_t* __restrict__ out, uint32_t n, uint32_t elem_words,
+                                                                ReduceBatchIdentity identity)
+{
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < n; s += gridDim.x * 256u)
+        for (uint32_t w = 0; w < elem_words; w++) out[(size_t) s * elem_words + w] = identity.w[w];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Short segments: a group of 1 << lg lanes per segment.
+// ---------------------------------------------------------------------------------------------------------
+template<int OP, typename S, int N>
+__global__ __launch_bounds__(kRbThreads) void reduce_batch_wave_kernel(const Elem<S, N>* __restrict__ data, Elem<S, N>* __restrict__ out,
+                                                                        ReduceBatchArgs a)
+{
+    using T = Elem<S, N>;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // device offsets: a third of the grid walks each short list; equal partitions: the whole grid, the one group size of `count`
+    const int sub = a.lists ? (int) (blockIdx.x % 3u) : a.sub;
+    const uint32_t block = a.lists ? blockIdx.x / 3u : blockIdx.x;
+    const uint32_t blocks = a.lists ? gridDim.x / 3u : gridDim.x;
+    const uint32_t lg = sub == RB_LIST_SHORT4 ? 2u : sub == RB_LIST_SHORT16 ? 4u : 6u;
+    const uint32_t G = 1u << lg, per_wave = kW >> lg;
+    const uint32_t n = a.lists ? reduce_batch_list_length(a, sub) : a.nsegs;
+    const uint32_t* list = a.lists ? a.lists + a.layout.start[sub] : nullptr;
+    const uint32_t j = lane & (G - 1u);
+
+    for (uint64_t first = (uint64_t) (block * kRbWaves + wave) * per_wave; first < n; first += (uint64_t) blocks * kRbWaves * per_wave)
+    {
+        const uint64_t li = first + (lane >> lg);
+        uint32_t seg = 0;
+        uint64_t begin = 0, len = 0;
+        if (li < n)
+        {
+            seg = list ? list[li] : (uint32_t) li;
+            reduce_batch_segment(a, seg, begin, len);
+        }
+        const T* p = data + begin;
+        T acc = zero_elem<S, N>();
+        bool has = false;
+        for (uint32_t i = j; i < (uint32_t) len; i += kRbUnroll * G)
+        {
+            T v[kRbUnroll];
+#pragma unroll
+            for (int u = 0; u < kRbUnroll; u++)
+                if (i + u * G < (uint32_t) len) v[u] = load_streaming(&p[i + u * G]);
+#pragma unroll
+            for (int u = 0; u < kRbUnroll; u++)
+                if (i + u * G < (uint32_t) len)
+                {
+                    acc = has ? combine<OP>(acc, v[u]) : v[u];
+                    has = true;
+                }
+        }
+#pragma unroll
+        for (uint32_t off = 32; off > 0; off >>= 1)
+        {
+            if (off >= G) continue; // wave-uniform
+            T o = shfl_down_t(acc, (int) off);
+            const int oh = __shfl_down((int) has, (int) off, kW);
+            const bool other_ok = (j + off < G) && oh;
+            if (other_ok) acc = has ? combine<OP>(acc, o) : o;
+            has = has || other_ok;
+        }
+        if (j == 0 && has) out[seg] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The fold of one contiguous range by a workgroup's threads: elements before the first 16-byte boundary and behind the last whole
+// 16-byte pack go one to a lane, the packs in between are read with 16-byte non-temporal loads, kRbUnroll in flight per lane.
+// ---------------------------------------------------------------------------------------------------------
+template<int OP, typename S, int N>
+__device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __restrict__ p, uint32_t len, uint32_t tid, Elem<S, N>& acc, bool& has)
+{
+    using T = Elem<S, N>;
+    constexpr uint32_t VEC = sizeof(T) < 16 ? 16 / (uint32_t) sizeof(T) : 1;
+    using P = Pack<T, (int) VEC>;
+    auto fold = [&](const T& v) {
+        acc = has ? combine<OP>(acc, v) : v;
+        has = true;
+    };
+    uint32_t head = 0;
+    if (VEC > 1)
+    {
+        head = (uint32_t) (((16u - (uint32_t) ((uintptr_t) p & 15u)) & 15u) / sizeof(T));
+        if (head > len) head = len;
+        if (tid < head) fold(p[tid]);
+    }
+    const P* packs = reinterpret_cast<const P*>(p + head);
+    const uint32_t npacks = (len - head) / VEC;
+    uint32_t i = tid;
+    for (; i + (kRbUnroll - 1) * kRbThreads < npacks; i += kRbUnroll * kRbThreads)
+    {
+        P v[kRbUnroll];
+#pragma unroll
+        for (int u = 0; u < kRbUnroll; u++) v[u] = load_streaming(&packs[i + u * kRbThreads]);
+#pragma unroll
+        for (int u = 0; u < kRbUnroll; u++)
+#pragma unroll
+            for (uint32_t k = 0; k < VEC; k++) fold(v[u].v[k]);
+    }
+    for (; i < npacks; i += kRbThreads)
+    {
+        const P v = load_streaming(&packs[i]);
+#pragma unroll
+        for (uint32_t k = 0; k < VEC; k++) fold(v.v[k]);
+    }
+    if (VEC > 1)
+    {
+        const uint32_t t = head + npacks * VEC + tid; // < VEC elements behind the last pack
+        if (t < len) fold(p[t]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Medium segments (combine == 0): src = the caller's array, one workgroup per entry of the medium list (or per partition).
+// Long segments' second step (combine == 1): src = the partials, one workgroup per entry of the long list (or per partition) folds
+// the segment's run of partials.
+// ---------------------------------------------------------------------------------------------------------
+template<int OP, typename S, int N>
+__global__ __launch_bounds__(kRbThreads) void reduce_batch_block_kernel(const Elem<S, N>* __restrict__ src, Elem<S, N>* __restrict__ out,
+                                                                         ReduceBatchArgs a, int combine_partials)
+{
+    using T = Elem<S, N>;
+    __shared__ T wtmp[kRbWaves];
+    __shared__ uint32_t whas[kRbWaves];
+    const uint32_t tid = threadIdx.x;
+    const int c = combine_partials ? RB_LIST_LONG : RB_LIST_BLOCK;
+    const uint32_t n = a.lists ? reduce_batch_list_length(a, c) : a.nsegs;
+    for (uint32_t li = blockIdx.x; li < n; li += gridDim.x)
+    {
+        uint32_t seg = li;
+        uint64_t begin, len;
+        if (!combine_partials)
+        {
+            if (a.lists) seg = a.lists[a.layout.start[RB_LIST_BLOCK] + li];
+            reduce_batch_segment(a, seg, begin, len);
+        }
+        else if (a.lists)
+        {
+            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[RB_LIST_LONG])[li];
+            seg = entry.x;
+            begin = entry.y;
+            uint64_t sb, sl;
+            reduce_batch_segment(a, seg, sb, sl);
+            len = (sl + a.layout.chunk - 1) / a.layout.chunk; // (a listed segment's whole run lies inside the chunk list)
+        }
+        else
+        {
+            begin = (uint64_t) li * a.chunks_per;
+            len = a.chunks_per;
+        }
+        T acc = zero_elem<S, N>();
+        bool has = false;
+        reduce_batch_fold_range<OP>(src + begin, (uint32_t) len, tid, acc, has);
+        bool rh;
+        const T r = block_reduce<OP>(acc, has, wtmp, whas, tid, rh);
+        if (tid == 0 && rh) out[seg] = r;
+        __syncthreads(); // wtmp / whas are read by every thread above and written again in the next round
+    }
+}
+
+// Long segments' first step: partials[slot] = fold of one chunk, one workgroup per entry of the chunk list (device offsets) or
+// per (partition, chunk) pair.
+template<int OP, typename S, int N>
+__global__ __launch_bounds__(kRbThreads) void reduce_batch_chunk_kernel(const Elem<S, N>* __restrict__ data, Elem<S, N>* __restrict__ partials,
+                                                                         ReduceBatchArgs a, uint64_t nitems)
+{
+    using T = Elem<S, N>;
+    __shared__ T wtmp[kRbWaves];
+    __shared__ uint32_t whas[kRbWaves];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = a.lists ? (uint64_t) reduce_batch_list_length(a, RB_LIST_CHUNKS) : nitems;
+    for (uint64_t slot = blockIdx.x; slot < n; slot += gridDim.x)
+    {
+        uint32_t seg, chunk;
+        if (a.lists)
+        {
+            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[RB_LIST_CHUNKS])[slot];
+            seg = entry.x;
+            chunk = entry.y;
+        }
+        else
+        {
+            seg = (uint32_t) (slot / a.chunks_per);
+            chunk = (uint32_t) (slot % a.chunks_per);
+        }
+        uint64_t begin, len;
+        reduce_batch_segment(a, seg, begin, len);
+        const uint64_t at = (uint64_t) chunk * a.layout.chunk;
+        T acc = zero_elem<S, N>();
+        bool has = false;
+        if (at < len) // (workgroup-uniform)
+        {
+            const uint64_t left = len - at;
+            reduce_batch_fold_range<OP>(data + begin + at, left < a.layout.chunk ? (uint32_t) left : a.layout.chunk, tid, acc, has);
+        }
+        bool rh;
+        const T r = block_reduce<OP>(acc, has, wtmp, whas, tid, rh);
+        if (tid == 0 && rh) partials[slot] = r;
+        __syncthreads();
+    }
+}
+
+} // namespace glu_hip

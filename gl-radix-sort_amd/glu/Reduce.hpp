@@ -47,6 +47,37 @@ namespace glu
             GLU_CHECK_STATUS(glu_reduce_run_ptr(m_impl, device_data, count, stream));
         }
 
+        /// Batched reduce (not in the reference; glu_reduce_run_batch_ptr in glu_hip.h): `num_partitions` adjacent partitions of
+        /// `count` elements each -- the shape of BlellochScan::operator() -- device_out[p] = the reduction of partition p, in one
+        /// asynchronous launch sequence.  Unlike operator() it only READS device_data; device_out (num_partitions elements of the
+        /// data type) must not overlap it.  An empty partition yields the operator's identity.
+        void reduce_batch(const void* device_data, void* device_out, size_t count, size_t num_partitions, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_reduce_run_batch_ptr(m_impl, device_data, device_out, count, num_partitions, stream));
+        }
+        /// The same for segments of any lengths: device_out[s] = the reduction of elements [offsets[s], offsets[s + 1]) of the
+        /// array of `total` elements; device_offsets is a DEVICE array of num_segments + 1 non-decreasing uint32 and is not read
+        /// by the host.
+        void reduce_batch_offsets(const void* device_data, void* device_out, size_t total, const uint32_t* device_offsets,
+                                  size_t num_segments, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_reduce_run_batch_offsets_ptr(m_impl, device_data, device_out, total, device_offsets, num_segments, stream));
+        }
+        /// Scratch for batched reduces of up to `total` elements in up to `num_segments` segments (they then allocate nothing and
+        /// can be captured into a graph).
+        void prepare_batch(size_t total, size_t num_segments) { GLU_CHECK_STATUS(glu_reduce_prepare_batch(m_impl, total, num_segments)); }
+        /// Segments each path of the last batched call took (glu_reduce_read_batch; synchronise its stream first).
+        struct BatchReport
+        {
+            uint32_t wave_segments = 0, block_segments = 0, long_segments = 0;
+        };
+        [[nodiscard]] BatchReport last_batch() const
+        {
+            BatchReport r;
+            GLU_CHECK_STATUS(glu_reduce_read_batch(m_impl, &r.wave_segments, &r.block_segments, &r.long_segments));
+            return r;
+        }
+
         [[nodiscard]] DataType data_type() const { return m_data_type; }
         [[nodiscard]] ReduceOperator reduce_operator() const { return m_operator; }
 

@@ -91,6 +91,11 @@ SYMBOLS = [
     ("glu_reduce_destroy", _int, [_vp]),
     ("glu_reduce_run", _int, [_vp, _u32, _sz]),
     ("glu_reduce_run_ptr", _int, [_vp, _vp, _sz, _vp]),
+    ("glu_reduce_run_batch_ptr", _int, [_vp, _vp, _vp, _sz, _sz, _vp]),
+    ("glu_reduce_run_batch_offsets_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    ("glu_reduce_prepare_batch", _int, [_vp, _sz, _sz]),
+    ("glu_reduce_plan_batch", _int, [_sz, _u32, _P(_u32), _P(_u32)]),
+    ("glu_reduce_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -258,6 +263,14 @@ def plan_batch(count, key_bytes=4, with_vals=True):
     do, 1 = a wave per partition, 2 = a workgroup per partition, 3 = longer than an LDS tile; tile in elements."""
     a, b = _u32(0), _u32(0)
     check(lib().glu_radix_sort_plan_batch(count, key_bytes, 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def plan_reduce_batch(count, elem_bytes=4):
+    """(path, workgroups) of a segment of `count` elements of `elem_bytes` bytes in a batched reduce (glu_reduce_plan_batch; host
+    only): path 0 = empty, 1 = a wave or part of one per segment, 2 = a workgroup per segment, 3 = several workgroups per segment."""
+    a, b = _u32(0), _u32(0)
+    check(lib().glu_reduce_plan_batch(count, elem_bytes, ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
 
 
@@ -476,6 +489,28 @@ class Reduce:
 
     def run_ptr(self, data_ptr, count, stream=None):
         check(lib().glu_reduce_run_ptr(self._h, _vp(data_ptr), count, _vp(stream)))
+
+    def run_batch_ptr(self, data_ptr, out_ptr, count, num_partitions, stream=None):
+        """out[p] = the reduction of partition p of `num_partitions` adjacent partitions of `count` elements; data is only read
+        (glu_reduce_run_batch_ptr)."""
+        check(lib().glu_reduce_run_batch_ptr(self._h, _vp(data_ptr), _vp(out_ptr), count, num_partitions, _vp(stream)))
+
+    def run_batch_offsets_ptr(self, data_ptr, out_ptr, total, offsets_ptr, num_segments, stream=None):
+        """out[s] = the reduction of elements [offsets[s], offsets[s+1]) (offsets: num_segments + 1 uint32 on the DEVICE); data is
+        only read (glu_reduce_run_batch_offsets_ptr)."""
+        check(lib().glu_reduce_run_batch_offsets_ptr(self._h, _vp(data_ptr), _vp(out_ptr), total, _vp(offsets_ptr), num_segments,
+                                                     _vp(stream)))
+
+    def prepare_batch(self, total, num_segments):
+        """Grow-only scratch for batched reduces of up to `total` elements in up to `num_segments` segments: after it the two
+        calls above allocate nothing (glu_reduce_prepare_batch)."""
+        check(lib().glu_reduce_prepare_batch(self._h, total, num_segments))
+
+    def read_batch(self):
+        """{wave, block, long}: segments each path of the last batched call took (glu_reduce_read_batch); synchronise first."""
+        a, b, c = _u32(0), _u32(0), _u32(0)
+        check(lib().glu_reduce_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"wave": a.value, "block": b.value, "long": c.value}
 
     def destroy(self):
         if self._h and _lib is not None:

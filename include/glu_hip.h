@@ -407,6 +407,62 @@ GLU_API glu_status glu_reduce_destroy(glu_reduce reduce);
 GLU_API glu_status glu_reduce_run(glu_reduce reduce, glu_buffer buffer, size_t count);
 GLU_API glu_status glu_reduce_run_ptr(glu_reduce reduce, void* data, size_t count, void* stream);
 
+/* ---- batched reduce (not in the reference, whose Reduce folds one array per call): out[s] = op over EVERY SEGMENT of an array,
+ * each on its own, in one asynchronous launch sequence, for all twelve glu_data_type's and four glu_reduce_operator's.
+ *   - `data` is READ ONLY: nothing is written to it.  This differs from glu_reduce_run_ptr, which works in place and leaves its
+ *     result in data[0].  `out` receives one element of the object's data type per segment (vector types: component-wise) and
+ *     must not overlap `data`; elements of `out` beyond the segments are not touched.  Both arrays must be aligned to the
+ *     element size, 16 bytes at most (the rule of glu_reduce_run_ptr).
+ *   - An EMPTY segment (count == 0, or equal offsets) yields the operator's identity: Sum 0, Mul 1, Min the largest value of the
+ *     scalar type (floats: +inf), Max its lowest value (floats: -inf).  num_partitions == 0 / num_segments == 0: nothing is done,
+ *     GLU_OK, NULL arrays are accepted.
+ *   - Equal partitions are indexed with 64 bits: count * num_partitions may exceed 2^32 (as in glu_scan_run_ptr and
+ *     glu_reduce_run_ptr); num_partitions must be < 2^31.  With device offsets total must be < 2^32 and num_segments <= 2^24
+ *     (the limits of the batched sort).
+ *   - `offsets` lives on the DEVICE and is never read by the host.  A segment whose end lies below its begin or beyond `total` is
+ *     empty to every kernel (its out element gets the identity), so nothing outside [0, total) of `data` is read whatever the
+ *     offsets hold, and every other segment still gets its result as long as those segments together hold no more than `total`
+ *     elements -- what non-decreasing offsets guarantee and what the segment lists are sized for.  Of segments that overlap each
+ *     other beyond that, those that found no room in the lists get NO result: their out elements keep what they held (which
+ *     ones depends on arrival order); a result that is written is always the whole segment's.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check: NULL reduce; NULL data or out with a non-zero size; NULL or
+ *     misaligned offsets; a misaligned array; out overlapping data; the limits above.
+ *   - Reproducible: the same call (same pointers, same shape, same contents) gives the same bits every time.  The order of
+ *     combination follows from the geometry alone -- a segment's address modulo 16, its length and its class -- with no atomics on
+ *     values and nothing combined in arrival order.  NaNs and the sign of a zero under Min / Max are unspecified, as in
+ *     glu_reduce_run_ptr.
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back of `offsets`, no side stream, and no device
+ *     allocation once glu_reduce_prepare_batch covered the sizes (else grow-only allocation inside the call, as in every other
+ *     entry point: not capturable).  The number of launches depends on the sizes passed by the host, never on the data: with
+ *     device offsets the list counts are cleared, a binning kernel writes the identity of empty segments and lists the others by
+ *     class, then one kernel folds the short segments, one the medium ones and two the long ones (at most six enqueued
+ *     operations); equal partitions take the one or two kernels of their class.
+ *   - Three classes by the BYTES of a segment (glu_reduce_plan_batch).  Up to 4 KiB a group of 4, 16 or 64 lanes of a wave folds
+ *     the segment (up to 16, up to 64, more elements): no barrier, no LDS.  Up to 256 KiB a workgroup folds it with 16-byte loads
+ *     from its first 16-byte-aligned element.  Longer segments are cut into chunks of 256 KiB: a workgroup per chunk writes a
+ *     partial result to the object's scratch, a second kernel folds each segment's partials in chunk order, so one long segment
+ *     occupies the whole device. */
+
+/* out[p] = op over data[p*count .. (p+1)*count), p < num_partitions (the shape of glu_scan_run_ptr) */
+GLU_API glu_status glu_reduce_run_batch_ptr(glu_reduce reduce, const void* data, void* out, size_t count,
+                                            size_t num_partitions, void* stream);
+/* out[s] = op over data[offsets[s] .. offsets[s+1]); offsets: DEVICE array of num_segments + 1 uint32, non-decreasing */
+GLU_API glu_status glu_reduce_run_batch_offsets_ptr(glu_reduce reduce, const void* data, void* out, size_t total,
+                                                    const uint32_t* offsets, size_t num_segments, void* stream);
+/* Grow-only scratch so that the two calls above allocate nothing (and can be captured) for batches of up to `total` (< 2^32)
+ * elements in up to `num_segments` (<= 2^24) segments: the segment lists (4 bytes per segment and class that fits `total`, 16
+ * bytes per 256 KiB chunk) and one partial result per chunk of the long class. */
+GLU_API glu_status glu_reduce_prepare_batch(glu_reduce reduce, size_t total, size_t num_segments);
+/* Host only, no device (unit-testable, like glu_radix_sort_plan_batch): the class of a segment of `count` elements of
+ * `elem_bytes` (4, 8, 16 or 32) bytes: path 0 = empty, 1 = a wave (or part of a wave) per segment, 2 = a workgroup per segment,
+ * 3 = several workgroups per segment; workgroups = how many one such segment is spread over (0 for an empty one).  Either
+ * pointer may be NULL. */
+GLU_API glu_status glu_reduce_plan_batch(size_t count, uint32_t elem_bytes, uint32_t* path, uint32_t* workgroups);
+/* Diagnostics of the last batched call on the object (the caller has synchronised its stream): how many segments each path took
+ * (empty ones take none).  Any pointer may be NULL. */
+GLU_API glu_status glu_reduce_read_batch(glu_reduce reduce, uint32_t* wave_segments, uint32_t* block_segments,
+                                         uint32_t* long_segments);
+
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
  * sharded form of glu::RadixSort::operator() (glu/RadixSort.hpp:273-334) that BASELINE.json configs[3] asks for.
