@@ -6,22 +6,11 @@
 
 #include "glu_host.hpp"
 #include "glu_reduce_object.hpp"
+#include "glu_scan_object.hpp"
 #include "scan_reduce_kernels.hpp"
 
 using namespace glu_hip;
 using namespace glu_hip::host;
-
-struct glu_scan_s
-{
-    glu_data_type type;
-    Scratch sums;
-    // chained (single-pass) scan state for 4-byte element types: one 64-bit word per chunk + a ticket counter
-    Scratch chain;
-    Scratch ticket;
-    uint32_t epoch = 0;
-    bool chained = true; // GLU_HIP_SCAN_CHAINED=0 falls back to reduce-then-scan
-    size_t chain_min_chunks = kChainMinChunks; // GLU_HIP_SCAN_CHAINED=2: chained from 2 chunks up (tests)
-};
 
 namespace
 {
@@ -247,6 +236,8 @@ glu_status glu_scan_destroy(glu_scan scan)
     scan->sums.release();
     scan->chain.release();
     scan->ticket.release();
+    scan->batch_lists.release();
+    scan->batch_partials.release();
     delete scan;
     return GLU_OK;
 }

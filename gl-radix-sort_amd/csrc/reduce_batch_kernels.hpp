@@ -118,10 +118,11 @@ __device__ __forceinline__ uint32_t reduce_batch_list_length(const ReduceBatchAr
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Binning (device offsets).  Empty segments get the identity here; every other segment is appended to the list of its class
+// Binning (device offsets; `static`, as `inline` is ignored on a kernel: the batched scan's translation unit includes this header too and bins with the same kernel,
+// elem_words = 0 and no `out`).  Empty segments get the identity here; every other segment is appended to the list of its class
 // (wave-aggregated: one atomic per wave and list), a long one also with one entry per chunk, written by the whole wave.
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatchArgs a, uint32_t* __restrict__ counts, uint32_t* __restrict__ lists,
+static __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatchArgs a, uint32_t* __restrict__ counts, uint32_t* __restrict__ lists,
                                                                uint32_t* __restrict__ out, uint32_t elem_words, ReduceBatchIdentity identity)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatchArgs a
 }
 
 // out[s] = identity for s < n (equal partitions of no elements)
-__global__ __launch_bounds__(256) void reduce_batch_fill_kernel(uint32_t* __restrict__ out, uint32_t n, uint32_t elem_words,
+static __global__ __launch_bounds__(256) void reduce_batch_fill_kernel(uint32_t* __restrict__ out, uint32_t n, uint32_t elem_words,
                                                                 ReduceBatchIdentity identity)
 {
     for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < n; s += gridDim.x * 256u)

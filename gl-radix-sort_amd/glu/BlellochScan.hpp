@@ -42,6 +42,29 @@ namespace glu
             GLU_CHECK_STATUS(glu_scan_run_ptr(m_impl, device_data, count, num_partitions, stream));
         }
 
+        /// Batched scan (not in the reference; glu_scan_run_batch_offsets_ptr in glu_hip.h): elements [offsets[s], offsets[s + 1])
+        /// of the array of `total` elements become their own exclusive scan, in place, for every s < num_segments, in one
+        /// asynchronous launch sequence.  device_offsets is a DEVICE array of num_segments + 1 non-decreasing uint32 and is not
+        /// read by the host; elements outside the segments are not touched.
+        void scan_batch_offsets(void* device_data, size_t total, const uint32_t* device_offsets, size_t num_segments, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_scan_run_batch_offsets_ptr(m_impl, device_data, total, device_offsets, num_segments, stream));
+        }
+        /// Scratch for batched scans of up to `total` elements in up to `num_segments` segments (they then allocate nothing and
+        /// can be captured into a graph).
+        void prepare_batch(size_t total, size_t num_segments) { GLU_CHECK_STATUS(glu_scan_prepare_batch(m_impl, total, num_segments)); }
+        /// Segments each path of the last batched call took (glu_scan_read_batch; synchronise its stream first).
+        struct BatchReport
+        {
+            uint32_t wave_segments = 0, block_segments = 0, long_segments = 0;
+        };
+        [[nodiscard]] BatchReport read_batch() const
+        {
+            BatchReport r;
+            GLU_CHECK_STATUS(glu_scan_read_batch(m_impl, &r.wave_segments, &r.block_segments, &r.long_segments));
+            return r;
+        }
+
         [[nodiscard]] DataType data_type() const { return m_data_type; }
 
     private:

@@ -87,6 +87,10 @@ SYMBOLS = [
     ("glu_scan_prepare", _int, [_vp, _sz, _sz]),
     ("glu_scan_run", _int, [_vp, _u32, _sz, _sz]),
     ("glu_scan_run_ptr", _int, [_vp, _vp, _sz, _sz, _vp]),
+    ("glu_scan_run_batch_offsets_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    ("glu_scan_prepare_batch", _int, [_vp, _sz, _sz]),
+    ("glu_scan_plan_batch", _int, [_sz, _u32, _P(_u32), _P(_u32)]),
+    ("glu_scan_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_reduce_create", _int, [_int, _int, _P(_vp)]),
     ("glu_reduce_destroy", _int, [_vp]),
     ("glu_reduce_run", _int, [_vp, _u32, _sz]),
@@ -271,6 +275,14 @@ def plan_reduce_batch(count, elem_bytes=4):
     only): path 0 = empty, 1 = a wave or part of one per segment, 2 = a workgroup per segment, 3 = several workgroups per segment."""
     a, b = _u32(0), _u32(0)
     check(lib().glu_reduce_plan_batch(count, elem_bytes, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def plan_scan_batch(count, elem_bytes=4):
+    """(path, workgroups) of a segment of `count` elements of `elem_bytes` bytes in a batched scan (glu_scan_plan_batch; host
+    only): path 0 = empty, 1 = a wave or part of one per segment, 2 = a workgroup per segment, 3 = several workgroups per segment."""
+    a, b = _u32(0), _u32(0)
+    check(lib().glu_scan_plan_batch(count, elem_bytes, ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
 
 
@@ -463,6 +475,22 @@ class BlellochScan:
 
     def run_ptr(self, data_ptr, count, num_partitions=1, stream=None):
         check(lib().glu_scan_run_ptr(self._h, _vp(data_ptr), count, num_partitions, _vp(stream)))
+
+    def run_batch_offsets_ptr(self, data_ptr, total, offsets_ptr, num_segments, stream=None):
+        """Elements [offsets[s], offsets[s+1]) become their own exclusive scan, in place, for every segment (offsets: num_segments
+        + 1 uint32 on the DEVICE) (glu_scan_run_batch_offsets_ptr)."""
+        check(lib().glu_scan_run_batch_offsets_ptr(self._h, _vp(data_ptr), total, _vp(offsets_ptr), num_segments, _vp(stream)))
+
+    def prepare_batch(self, total, num_segments):
+        """Grow-only scratch for batched scans of up to `total` elements in up to `num_segments` segments: after it the call
+        above allocates nothing (glu_scan_prepare_batch)."""
+        check(lib().glu_scan_prepare_batch(self._h, total, num_segments))
+
+    def read_batch(self):
+        """{wave, block, long}: segments each path of the last batched call took (glu_scan_read_batch); synchronise first."""
+        a, b, c = _u32(0), _u32(0), _u32(0)
+        check(lib().glu_scan_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return {"wave": a.value, "block": b.value, "long": c.value}
 
     def destroy(self):
         if self._h and _lib is not None:

@@ -396,6 +396,57 @@ GLU_API glu_status glu_scan_run(glu_scan scan, glu_buffer buffer, size_t count, 
  * results are exact either way); GLU_HIP_SCAN_CHAINED=0 selects the reproducible form. */
 GLU_API glu_status glu_scan_run_ptr(glu_scan scan, void* data, size_t count, size_t num_partitions, void* stream);
 
+/* ---- batched scan (not in the reference, whose BlellochScan takes equal power-of-two partitions): EVERY SEGMENT of an array
+ * replaced by its own exclusive `+` scan (identity 0), in place, in one asynchronous launch sequence, for all twelve
+ * glu_data_type's.  Segment s is [offsets[s], offsets[s+1]), in elements of the object's data type.  Equal partitions have no
+ * entry point of their own here: glu_scan_run_ptr is that entry point.
+ *   - Result: element i of segment s receives the sum of elements [offsets[s], i) of the segment's ORIGINAL contents,
+ *     component-wise for vector types.  The first element of a non-empty segment becomes 0.  Integer types are exact modulo 2^32.
+ *     A float result is a sum of exactly those elements, in an order fixed by the geometry alone: the segment's address modulo
+ *     16, its length and its class.  The same call (same pointers, same shape, same contents) gives the same bits every time: no
+ *     atomics on values and no look-back in ticket or arrival order on this path (unlike the chained form of glu_scan_run_ptr).
+ *   - Elements outside [offsets[0], offsets[num_segments]) are not touched.  Empty segments are legal anywhere.
+ *     num_segments == 0: nothing is done, GLU_OK, NULL arrays are accepted.
+ *   - Limits (those of the batched sort and the batched reduce): total < 2^32, num_segments <= 2^24, `data` aligned to its
+ *     element size, 16 bytes at most, `offsets` 4-byte aligned.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check: NULL scan; NULL data with a non-zero total; NULL or misaligned
+ *     offsets; misaligned data; the limits above.
+ *   - `offsets` lives on the DEVICE and is never read by the host.  A segment whose end lies below its begin or beyond `total` is
+ *     empty to every kernel, and no kernel reads or writes outside [0, total) of `data` whatever the offsets hold: list lengths
+ *     and chunk slots are clamped to the lists' capacity, the chunk slots come from a 64-bit counter that cannot wrap (the
+ *     batched reduce's lists and clamps).  Which elements of [0, total) change under malformed or overlapping offsets is
+ *     unspecified, as in the batched sort.
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back of `offsets`, no side stream, and no device
+ *     allocation once glu_scan_prepare_batch covered the sizes (else grow-only allocation inside the call, as in every other
+ *     entry point: not capturable).  The number of enqueued operations depends on `total` and `num_segments` as passed by the
+ *     host, never on the data: the list counts are cleared, a binning kernel lists the segments by class, then one kernel scans
+ *     the short segments, one the medium ones and three the long ones (at most seven enqueued operations; a class that no
+ *     segment of a batch of `total` elements can belong to is skipped).
+ *   - Three classes by the BYTES of a segment (glu_scan_plan_batch).  Up to 2 KiB a group of 4, 16 or 64 lanes of a wave holds
+ *     the segment in registers (up to 128 bytes, up to 512 bytes, more): no barrier, no LDS.  Up to 64 KiB a workgroup scans it
+ *     tile after tile with a running carry, with 16-byte accesses from its first 16-byte-aligned element: every element is read
+ *     once and written once.  Longer segments are cut into chunks of 32 KiB: a workgroup per chunk writes the chunk's sum to the
+ *     object's scratch, a second kernel scans each segment's sums in chunk order, a third scans every chunk with its sum of the
+ *     chunks before it as carry-in, so one long segment occupies the whole device (three passes over memory instead of two). */
+
+/* data[offsets[s] .. offsets[s+1]) = its own exclusive + scan, in place, for every s < num_segments;
+ * offsets: DEVICE array of num_segments + 1 uint32, non-decreasing, in elements of the object's data type */
+GLU_API glu_status glu_scan_run_batch_offsets_ptr(glu_scan scan, void* data, size_t total, const uint32_t* offsets,
+                                                  size_t num_segments, void* stream);
+/* Grow-only scratch so that the call above allocates nothing (and can be captured) for batches of up to `total` (< 2^32) elements
+ * in up to `num_segments` (<= 2^24) segments: the segment lists (4 bytes per segment and class that fits `total`, 16 bytes per
+ * 32 KiB chunk) and one partial sum per chunk of the long class. */
+GLU_API glu_status glu_scan_prepare_batch(glu_scan scan, size_t total, size_t num_segments);
+/* Host only, no device (unit-testable, like glu_reduce_plan_batch): the class of a segment of `count` elements of `elem_bytes`
+ * (4, 8, 16 or 32) bytes: path 0 = nothing to do, 1 = a wave (or part of a wave) per segment, 2 = a workgroup per segment,
+ * 3 = several workgroups per segment; workgroups = how many one such segment is spread over (0 for an empty one), as in
+ * glu_reduce_plan_batch.  Either pointer may be NULL. */
+GLU_API glu_status glu_scan_plan_batch(size_t count, uint32_t elem_bytes, uint32_t* path, uint32_t* workgroups);
+/* Diagnostics of the last batched call on the object (the caller has synchronised its stream): how many segments each path took
+ * (empty ones take none).  Any pointer may be NULL. */
+GLU_API glu_status glu_scan_read_batch(glu_scan scan, uint32_t* wave_segments, uint32_t* block_segments,
+                                       uint32_t* long_segments);
+
 /* ---- reduce: replaces glu::Reduce (glu/Reduce.hpp:51-136) ----------------------------------------- */
 
 /* Reduce::Reduce(data_type, operator)                  (Reduce.hpp:62-107) */
