@@ -10,6 +10,7 @@
 //   glu_scan_reduce.hip       BlellochScan and Reduce
 //   glu_reduce_batch.hip      the batched reduce: every segment of an array folded on its own (reduce_batch_kernels.hpp)
 //   glu_scan_batch.hip        the batched scan: every segment of an array scanned on its own (scan_batch_kernels.hpp)
+// The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 

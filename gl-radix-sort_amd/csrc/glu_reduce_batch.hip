@@ -8,7 +8,7 @@
 #include <limits>
 #include <type_traits>
 
-#include "glu_host.hpp"
+#include "glu_batch_host.hpp"
 #include "glu_reduce_object.hpp"
 #include "reduce_batch_kernels.hpp"
 
@@ -17,37 +17,11 @@ using namespace glu_hip::host;
 
 namespace
 {
-constexpr size_t kBatchMaxSegments = (size_t) 1 << 24;
-constexpr uint32_t kBatchCountWords = 64; // the list counts in front of the lists, on a line of their own
-
-// The lists of a batch with device offsets.  A segment list can hold as many segments as fit `total` at its class's shortest
-// length; the long list as many segments longer than a chunk; the chunk list a chunk per whole chunk of `total` and one more per
-// long segment (its last, partial one).  Equal partitions of the long class need no more partials than the chunk list has slots.
-ReduceBatchLayout lists_layout(size_t total, size_t num_segments, size_t elem_bytes, size_t& words)
+// the classes of a batch with device offsets
+BatchClasses classes_of(size_t elem_bytes)
 {
-    ReduceBatchLayout l;
-    l.limit[RB_LIST_SHORT4] = kRbGroup4Elems;
-    l.limit[RB_LIST_SHORT16] = kRbGroup16Elems;
-    l.limit[RB_LIST_SHORT64] = kRbWaveBytes / (uint32_t) elem_bytes;
-    l.limit[RB_LIST_BLOCK] = kRbBlockBytes / (uint32_t) elem_bytes;
-    l.chunk = kRbChunkBytes / (uint32_t) elem_bytes;
-    size_t at = 0;
-    for (int c = 0; c <= RB_LIST_BLOCK; c++)
-    {
-        const size_t shortest = c == 0 ? 1 : (size_t) l.limit[c - 1] + 1;
-        l.start[c] = (uint32_t) at;
-        l.capacity[c] = (uint32_t) std::min<size_t>(num_segments, total / shortest);
-        at += l.capacity[c];
-    }
-    at = (at + 1) & ~(size_t) 1; // the entries of the last two lists are 8 bytes
-    l.start[RB_LIST_LONG] = (uint32_t) at;
-    l.capacity[RB_LIST_LONG] = (uint32_t) std::min<size_t>(num_segments, total / ((size_t) l.limit[RB_LIST_BLOCK] + 1));
-    at += 2 * (size_t) l.capacity[RB_LIST_LONG];
-    l.start[RB_LIST_CHUNKS] = (uint32_t) at;
-    l.capacity[RB_LIST_CHUNKS] = (uint32_t) (total / l.chunk + l.capacity[RB_LIST_LONG]);
-    at += 2 * (size_t) l.capacity[RB_LIST_CHUNKS];
-    words = kBatchCountWords + at;
-    return l;
+    const uint32_t es = (uint32_t) elem_bytes;
+    return {1, {kRbGroup4Elems, kRbGroup16Elems, kRbWaveBytes / es, kRbBlockBytes / es}, kRbChunkBytes / es, true};
 }
 
 template<int OP, typename S, int N>
@@ -64,10 +38,8 @@ ReduceBatchIdentity identity_of()
     return id;
 }
 
-inline uint32_t cus() { return (uint32_t) g_dev.num_cus; }
-
 // which short list (= group size) equal partitions of `count` elements take
-inline int short_sub(size_t count) { return count <= kRbGroup4Elems ? RB_LIST_SHORT4 : count <= kRbGroup16Elems ? RB_LIST_SHORT16 : RB_LIST_SHORT64; }
+inline int short_sub(size_t count) { return count <= kRbGroup4Elems ? BATCH_LIST_SHORT4 : count <= kRbGroup16Elems ? BATCH_LIST_SHORT16 : BATCH_LIST_SHORT64; }
 
 struct BatchCall
 {
@@ -86,10 +58,9 @@ glu_status run_equal(const BatchCall& c)
     glu_reduce_s* r = c.red;
     uint32_t path, workgroups;
     reduce_batch_plan(c.count, sizeof(T), path, workgroups);
-    r->last_batch_on_device = false;
-    r->last_batch[0] = r->last_batch[1] = r->last_batch[2] = 0;
-    if (path) r->last_batch[path - 1] = (uint32_t) c.num_segments;
-    ReduceBatchArgs a = {};
+    r->last_batch.reset();
+    if (path) r->last_batch.by_class[path - 1] = (uint32_t) c.num_segments;
+    BatchListsArgs a = {};
     a.count = c.count;
     a.nsegs = (uint32_t) c.num_segments;
     a.layout.chunk = kRbChunkBytes / (uint32_t) sizeof(T);
@@ -104,7 +75,7 @@ glu_status run_equal(const BatchCall& c)
     else if (path == 1)
     {
         a.sub = short_sub(c.count);
-        const uint32_t per_block = kRbWaves * (a.sub == RB_LIST_SHORT4 ? 16u : a.sub == RB_LIST_SHORT16 ? 4u : 1u);
+        const uint32_t per_block = kRbWaves * (a.sub == BATCH_LIST_SHORT4 ? 16u : a.sub == BATCH_LIST_SHORT16 ? 4u : 1u);
         const uint32_t grid = (uint32_t) std::min<uint64_t>(((uint64_t) a.nsegs + per_block - 1) / per_block, cus() * 8u);
         hipLaunchKernelGGL((reduce_batch_wave_kernel<OP, S, N>), dim3(grid), dim3(kRbThreads), 0, c.stream, data, out, a);
     }
@@ -130,11 +101,9 @@ glu_status run_equal(const BatchCall& c)
     return GLU_OK;
 }
 
-glu_status reserve_batch(glu_reduce_s* r, size_t total, size_t num_segments, size_t elem_bytes, ReduceBatchLayout& layout)
+// what a batch with device offsets needs beside its lists: the partials of the long segments' chunks
+glu_status reserve_partials(glu_reduce_s* r, size_t total, size_t num_segments, const BatchListsLayout& layout, size_t elem_bytes)
 {
-    size_t words;
-    layout = lists_layout(total, num_segments, elem_bytes, words);
-    GLU_TRY(r->batch_lists.reserve(words * sizeof(uint32_t)));
     // (equal partitions of the long class: at most total / chunk + num_segments chunks, and they are longer than a chunk)
     const size_t slots = total / layout.chunk + std::min<size_t>(num_segments, total / layout.chunk);
     if (slots) GLU_TRY(r->batch_partials.reserve(slots * elem_bytes));
@@ -148,46 +117,38 @@ glu_status run_offsets(const BatchCall& c)
 {
     using T = Elem<S, N>;
     glu_reduce_s* r = c.red;
-    ReduceBatchArgs a = {};
-    GLU_TRY(reserve_batch(r, c.total, c.num_segments, sizeof(T), a.layout));
-    uint32_t* const image = (uint32_t*) r->batch_lists.ptr;
+    BatchListsArgs a = {};
+    uint32_t *counts, *lists, bin_grid;
+    GLU_TRY(begin_batch_offsets(r->batch_lists, classes_of(sizeof(T)), c.total, c.num_segments, c.stream, a.layout, counts, lists, bin_grid));
+    GLU_TRY(reserve_partials(r, c.total, c.num_segments, a.layout, sizeof(T)));
     a.offsets = c.offsets;
     a.total = (uint32_t) c.total;
     a.nsegs = (uint32_t) c.num_segments;
-    a.counts = image;
-    a.lists = image + kBatchCountWords;
+    a.counts = counts;
+    a.lists = lists;
     const T* data = (const T*) c.data;
     T* out = (T*) c.out;
     T* partials = (T*) r->batch_partials.ptr;
-    HIP_TRY(hipMemsetAsync(image, 0, kBatchCountWords * sizeof(uint32_t), c.stream));
-    const uint32_t bin_grid = std::min<uint32_t>((a.nsegs + 255u) / 256u, cus() * 4u);
-    hipLaunchKernelGGL(reduce_batch_bin_kernel, dim3(bin_grid), dim3(256), 0, c.stream, a, image, image + kBatchCountWords, (uint32_t*) c.out,
+    hipLaunchKernelGGL(reduce_batch_bin_kernel, dim3(bin_grid), dim3(256), 0, c.stream, a, counts, lists, (uint32_t*) c.out,
                        (uint32_t) (sizeof(T) / 4), identity_of<OP, S, N>());
     HIP_TRY(hipGetLastError());
-    r->last_batch_on_device = true;
+    r->last_batch.on_device = true;
     if (c.total == 0) return GLU_OK; // every segment is empty
-    // a third of the grid per short list: a workgroup's four waves hold 64 / 16 / 4 segments of the three lists at a time
-    uint32_t short_blocks = 1;
-    for (int s = RB_LIST_SHORT4; s <= RB_LIST_SHORT64; s++)
-    {
-        const uint32_t per_block = kRbWaves * (s == RB_LIST_SHORT4 ? 16u : s == RB_LIST_SHORT16 ? 4u : 1u);
-        short_blocks = std::max<uint32_t>(short_blocks, (uint32_t) (((uint64_t) a.layout.capacity[s] + per_block - 1) / per_block));
-    }
-    short_blocks = std::min<uint32_t>(short_blocks, cus() * 8u);
-    hipLaunchKernelGGL((reduce_batch_wave_kernel<OP, S, N>), dim3(3u * short_blocks), dim3(kRbThreads), 0, c.stream, data, out, a);
+    hipLaunchKernelGGL((reduce_batch_wave_kernel<OP, S, N>), dim3(3u * short_lists_blocks(a.layout, kRbWaves)), dim3(kRbThreads), 0, c.stream,
+                       data, out, a);
     HIP_TRY(hipGetLastError());
-    if (a.layout.capacity[RB_LIST_BLOCK])
+    if (a.layout.capacity[BATCH_LIST_BLOCK])
     {
-        hipLaunchKernelGGL((reduce_batch_block_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[RB_LIST_BLOCK], cus() * 8u)),
+        hipLaunchKernelGGL((reduce_batch_block_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[BATCH_LIST_BLOCK], cus() * 8u)),
                            dim3(kRbThreads), 0, c.stream, data, out, a, 0);
         HIP_TRY(hipGetLastError());
     }
-    if (a.layout.capacity[RB_LIST_LONG])
+    if (a.layout.capacity[BATCH_LIST_LONG])
     {
-        hipLaunchKernelGGL((reduce_batch_chunk_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[RB_LIST_CHUNKS], cus() * 8u)),
+        hipLaunchKernelGGL((reduce_batch_chunk_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[BATCH_LIST_CHUNKS], cus() * 8u)),
                            dim3(kRbThreads), 0, c.stream, data, partials, a, (uint64_t) 0);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL((reduce_batch_block_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[RB_LIST_LONG], cus() * 8u)),
+        hipLaunchKernelGGL((reduce_batch_block_kernel<OP, S, N>), dim3(std::min<uint32_t>(a.layout.capacity[BATCH_LIST_LONG], cus() * 8u)),
                            dim3(kRbThreads), 0, c.stream, (const T*) partials, out, a, 1);
         HIP_TRY(hipGetLastError());
     }
@@ -245,10 +206,12 @@ glu_status glu_reduce_prepare_batch(glu_reduce reduce, size_t total, size_t num_
 {
     GLU_TRY(enter());
     if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
-    if (total >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "a prepared batch must hold fewer than 2^32 elements (got %zu)", total);
-    if (num_segments > kBatchMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %zu exceeds 2^24", num_segments);
-    ReduceBatchLayout layout;
-    return reserve_batch(reduce, total, num_segments, data_type_size(reduce->type), layout);
+    GLU_TRY(check_batch_total(total));
+    GLU_TRY(check_batch_segments(num_segments));
+    const size_t elem_bytes = data_type_size(reduce->type);
+    BatchListsLayout layout;
+    GLU_TRY(reserve_batch_lists(reduce->batch_lists, classes_of(elem_bytes), total, num_segments, layout));
+    return reserve_partials(reduce, total, num_segments, layout, elem_bytes);
 }
 
 glu_status glu_reduce_run_batch_ptr(glu_reduce reduce, const void* data, void* out, size_t count, size_t num_partitions, void* stream)
@@ -260,8 +223,7 @@ glu_status glu_reduce_run_batch_ptr(glu_reduce reduce, const void* data, void* o
     GLU_TRY(check_arrays(reduce, data, out, count * num_partitions, num_partitions));
     if (num_partitions == 0)
     {
-        reduce->last_batch_on_device = false;
-        reduce->last_batch[0] = reduce->last_batch[1] = reduce->last_batch[2] = 0;
+        reduce->last_batch.reset();
         return GLU_OK;
     }
     BatchRunner r{{reduce, data, out, count, num_partitions, count * num_partitions, nullptr, pick_stream(stream)}};
@@ -273,15 +235,13 @@ glu_status glu_reduce_run_batch_offsets_ptr(glu_reduce reduce, const void* data,
 {
     GLU_TRY(enter());
     if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
-    if (total >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "a batch with offsets must hold fewer than 2^32 elements (got %zu)", total);
-    if (num_segments > kBatchMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %zu exceeds 2^24", num_segments);
+    GLU_TRY(check_batch_total(total));
+    GLU_TRY(check_batch_segments(num_segments));
     GLU_TRY(check_arrays(reduce, data, out, num_segments ? total : 0, num_segments));
-    if (num_segments && !offsets) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid offsets array");
-    if ((uintptr_t) offsets % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the offsets array is not aligned to its element size");
+    GLU_TRY(check_batch_offsets(offsets, num_segments));
     if (num_segments == 0)
     {
-        reduce->last_batch_on_device = false;
-        reduce->last_batch[0] = reduce->last_batch[1] = reduce->last_batch[2] = 0;
+        reduce->last_batch.reset();
         return GLU_OK;
     }
     BatchRunner r{{reduce, data, out, 0, num_segments, total, offsets, pick_stream(stream)}};
@@ -292,19 +252,7 @@ glu_status glu_reduce_read_batch(glu_reduce reduce, uint32_t* wave_segments, uin
 {
     GLU_TRY(enter());
     if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
-    uint32_t by_class[3] = {reduce->last_batch[0], reduce->last_batch[1], reduce->last_batch[2]};
-    if (reduce->last_batch_on_device)
-    {
-        uint32_t counts[kRbCounts];
-        HIP_TRY(hipMemcpy(counts, reduce->batch_lists.ptr, sizeof(counts), hipMemcpyDeviceToHost));
-        by_class[0] = counts[RB_LIST_SHORT4] + counts[RB_LIST_SHORT16] + counts[RB_LIST_SHORT64];
-        by_class[1] = counts[RB_LIST_BLOCK];
-        by_class[2] = counts[kRbCountLong];
-    }
-    if (wave_segments) *wave_segments = by_class[0];
-    if (block_segments) *block_segments = by_class[1];
-    if (long_segments) *long_segments = by_class[2];
-    return GLU_OK;
+    return reduce->last_batch.read(reduce->batch_lists, 3, wave_segments, block_segments, long_segments); // (the three short lists)
 }
 
 } // extern "C"

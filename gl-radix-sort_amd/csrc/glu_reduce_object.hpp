@@ -2,7 +2,7 @@
 // object (glu_scan_reduce.hip owns its life, glu_reduce_batch.hip its batched calls) and the dispatch over the twelve data types.
 #pragma once
 
-#include "glu_host.hpp"
+#include "glu_batch_host.hpp"
 
 struct glu_reduce_s
 {
@@ -12,8 +12,7 @@ struct glu_reduce_s
     // the batched reduce: the list counts and the segment lists of a call with device offsets; the per-chunk partials of long segments
     glu_hip::host::Scratch batch_lists;
     glu_hip::host::Scratch batch_partials;
-    uint32_t last_batch[3] = {0, 0, 0}; // segments per class of the last batched call, when the host knew them (equal partitions)
-    bool last_batch_on_device = false;  // ... else the counts lie in batch_lists
+    glu_hip::host::LastBatch last_batch; // segments per class of the last batched call (glu_reduce_read_batch)
 };
 
 namespace glu_hip

@@ -2,7 +2,7 @@
 // its life and the single scan, glu_scan_batch.hip its batched calls.
 #pragma once
 
-#include "glu_host.hpp"
+#include "glu_batch_host.hpp"
 #include "scan_reduce_kernels.hpp"
 
 struct glu_scan_s
@@ -18,5 +18,5 @@ struct glu_scan_s
     // the batched scan: the list counts and the segment lists of a call; the per-chunk partials of long segments
     glu_hip::host::Scratch batch_lists;
     glu_hip::host::Scratch batch_partials;
-    bool last_batch_on_device = false; // the counts of the last batched call lie in batch_lists (else it listed nothing)
+    glu_hip::host::LastBatch last_batch; // segments per class of the last batched call (glu_scan_read_batch)
 };

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <mutex>
 
-#include "glu_host.hpp"
+#include "glu_batch_host.hpp"
 #include "glu_sort_object.hpp"
 #include "radix_batch_kernels.hpp"
 
@@ -15,9 +15,6 @@ using namespace glu_hip::host;
 
 namespace
 {
-constexpr size_t kBatchMaxSegments = (size_t) 1 << 24;
-constexpr uint32_t kBatchCountWords = 64; // the list counts (kBatchLists words) in front of the lists, on a line of their own
-
 // The tiles of the workgroup class (elements): 256 x 4, 1024 x 4 and the single-block limit (1024 x 16; 8-byte keys: 1024 x 8).
 constexpr uint32_t batch_block_tile(int geo, size_t key_bytes)
 {
@@ -36,23 +33,10 @@ void plan_equal(size_t count, size_t key_bytes, uint32_t& path, uint32_t& tile, 
     tile = batch_block_tile(2, key_bytes);
 }
 
-// the lists of a batch with device offsets: list c can hold as many segments as fit `total` at the class's shortest length
-BatchLists lists_layout(size_t total, size_t num_segments, size_t key_bytes, size_t& words)
+// the classes of a batch with device offsets: segments of 2 elements and more; the wave class, the three tiles, longer ones
+BatchClasses classes_of(size_t key_bytes)
 {
-    BatchLists l;
-    l.limit[0] = kBatchWaveTile;
-    for (int g = 0; g < 3; g++) l.limit[1 + g] = batch_block_tile(g, key_bytes);
-    l.limit[kBatchLists - 1] = 0xFFFFFFFFu;
-    size_t at = 0;
-    for (int c = 0; c < kBatchLists; c++)
-    {
-        const size_t shortest = c == 0 ? 2 : (size_t) l.limit[c - 1] + 1;
-        l.start[c] = (uint32_t) at;
-        l.capacity[c] = (uint32_t) std::min<size_t>(num_segments, total / shortest);
-        at += l.capacity[c];
-    }
-    words = kBatchCountWords + at; // the counts, then the lists
-    return l;
+    return {2, {kBatchWaveTile, batch_block_tile(0, key_bytes), batch_block_tile(1, key_bytes), batch_block_tile(2, key_bytes)}, 0, false};
 }
 
 template<typename KeyT, int THREADS, int KPT, bool VALS>
@@ -75,7 +59,7 @@ struct BatchArgs
     uint32_t count = 0, total = 0, xf = 0;
     const uint32_t* lists = nullptr;   // device lists of a batch with device offsets (NULL: the segments themselves)
     const uint32_t* counts = nullptr;
-    BatchLists layout = {};
+    BatchListsLayout layout = {};
     uint32_t nsegs = 0;                // equal partitions: their number
 };
 
@@ -83,7 +67,7 @@ struct BatchArgs
 inline void list_of(const BatchArgs& a, int c, const uint32_t*& list, const uint32_t*& list_count, uint32_t& capacity)
 {
     list = a.lists ? a.lists + a.layout.start[c] : nullptr;
-    list_count = a.lists ? a.counts + c : nullptr;
+    list_count = a.lists ? a.counts + batch_count_word(c) : nullptr;
     capacity = a.lists ? a.layout.capacity[c] : a.nsegs;
 }
 
@@ -141,7 +125,7 @@ glu_status launch_long(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, const Ba
 {
     const uint32_t *list, *list_count;
     uint32_t capacity;
-    list_of(a, kBatchLists - 1, list, list_count, capacity);
+    list_of(a, BATCH_LIST_LONG, list, list_count, capacity);
     if (!capacity) return GLU_OK;
     const uint32_t grid = std::min<uint32_t>(capacity, (uint32_t) g_dev.num_cus);
     hipLaunchKernelGGL((radix_batch_long_kernel<KeyT, VALS>), dim3(grid), dim3(1024), 0, stream, keys, vals, (KeyT*) s->keys.ptr,
@@ -150,39 +134,28 @@ glu_status launch_long(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, const Ba
     return GLU_OK;
 }
 
-glu_status reserve_batch(glu_radix_sort_s* s, size_t total, size_t num_segments, size_t key_bytes, bool with_vals)
-{
-    size_t words;
-    (void) lists_layout(total, num_segments, key_bytes, words);
-    GLU_TRY(s->batch_lists.reserve(words * sizeof(uint32_t)));
-    // the long class sorts between the caller's arrays and the object's scratch arrays
-    return sort_prepare_plain(s, total, key_bytes, with_vals);
-}
-
 // device offsets: binning, then one kernel per list; seven launches whatever the segments look like
 template<typename KeyT, bool VALS>
 glu_status run_offsets(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t total, const uint32_t* offsets, size_t num_segments,
                        uint32_t xf, hipStream_t stream)
 {
-    GLU_TRY(reserve_batch(s, total, num_segments, sizeof(KeyT), VALS));
-    size_t words;
+    // the long class sorts between the caller's arrays and the object's scratch arrays
+    GLU_TRY(sort_prepare_plain(s, total, sizeof(KeyT), VALS));
     BatchArgs a;
-    a.layout = lists_layout(total, num_segments, sizeof(KeyT), words);
     a.offsets = offsets;
     a.total = (uint32_t) total;
     a.xf = xf;
-    uint32_t* const image = (uint32_t*) s->batch_lists.ptr;
-    a.counts = image;
-    a.lists = image + kBatchCountWords;
-    HIP_TRY(hipMemsetAsync(image, 0, kBatchCountWords * sizeof(uint32_t), stream));
-    const uint32_t bin_grid = std::min<uint32_t>((uint32_t) ((num_segments + 255) / 256), (uint32_t) g_dev.num_cus * 4u);
+    uint32_t *counts, *lists, bin_grid;
+    GLU_TRY(begin_batch_offsets(s->batch_lists, classes_of(sizeof(KeyT)), total, num_segments, stream, a.layout, counts, lists, bin_grid));
+    a.counts = counts;
+    a.lists = lists;
     hipLaunchKernelGGL(radix_batch_bin_kernel, dim3(bin_grid), dim3(256), 0, stream, offsets, (uint32_t) num_segments, (uint32_t) total,
-                       a.layout, image, image + kBatchCountWords);
+                       a.layout, counts, lists);
     HIP_TRY(hipGetLastError());
     GLU_TRY((launch_wave<KeyT, VALS>(keys, vals, a, stream)));
     for (int geo = 0; geo < 3; geo++) GLU_TRY((launch_block<KeyT, VALS>(keys, vals, a, geo, stream)));
     GLU_TRY((launch_long<KeyT, VALS>(s, keys, vals, a, stream)));
-    s->last_batch_on_device = true;
+    s->last_batch.on_device = true;
     return GLU_OK;
 }
 
@@ -217,7 +190,7 @@ glu_status check_arrays(const void* keys, const uint32_t* vals, size_t elements,
 {
     if ((int) key_type < (int) GLU_KEY_UINT32 || (int) key_type > (int) GLU_KEY_FLOAT64)
         return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", (int) key_type);
-    if (elements >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "a batch must hold fewer than 2^32 elements (got %zu)", elements);
+    GLU_TRY(check_batch_total(elements));
     if (elements && !keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
     if ((uintptr_t) keys % key_bytes_of(key_type)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the key array is not aligned to its element size");
     if ((uintptr_t) vals % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the value array is not aligned to its element size");
@@ -244,12 +217,11 @@ glu_status glu_radix_sort_prepare_batch(glu_radix_sort sort, size_t total, size_
     GLU_TRY(enter());
     if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
     if (key_bytes != 4 && key_bytes != 8) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bytes must be 4 or 8 (got %zu)", key_bytes);
-    if (total >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "a batch must hold fewer than 2^32 elements (got %zu)", total);
-    if (num_segments > kBatchMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %zu exceeds 2^24", num_segments);
-    size_t words;
-    (void) lists_layout(total, num_segments, key_bytes, words);
-    GLU_TRY(sort->batch_lists.reserve(words * sizeof(uint32_t)));
-    GLU_TRY(glu_radix_sort_prepare_ex(sort, total, key_bytes, with_vals));
+    GLU_TRY(check_batch_total(total));
+    GLU_TRY(check_batch_segments(num_segments));
+    BatchListsLayout layout;
+    GLU_TRY(reserve_batch_lists(sort->batch_lists, classes_of(key_bytes), total, num_segments, layout));
+    GLU_TRY(glu_radix_sort_prepare_ex(sort, total, key_bytes, with_vals)); // (the scratch arrays of the long class)
     // the LDS opt-in of the workgroup class's kernels, so that a first call under stream capture finds it made
     if (key_bytes == 4) return with_vals ? block_opt_in_all<uint32_t, true>() : block_opt_in_all<uint32_t, false>();
     return with_vals ? block_opt_in_all<uint64_t, true>() : block_opt_in_all<uint64_t, false>();
@@ -262,15 +234,14 @@ glu_status glu_radix_sort_run_batch_ptr(glu_radix_sort sort, void* keys, uint32_
     if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
     if (count && num_partitions > ((size_t) -1) / count) return fail(GLU_ERROR_INVALID_ARGUMENT, "count * num_partitions overflows");
     GLU_TRY(check_arrays(keys, vals, count * num_partitions, key_type));
-    if (num_partitions > kBatchMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_partitions %zu exceeds 2^24", num_partitions);
+    GLU_TRY(check_batch_segments(num_partitions));
     const size_t key_bytes = key_bytes_of(key_type);
     uint32_t path, tile;
     int geo;
     plan_equal(count, key_bytes, path, tile, geo);
-    sort->last_batch_on_device = false;
-    sort->last_batch[0] = sort->last_batch[1] = sort->last_batch[2] = 0;
+    sort->last_batch.reset();
     if (path == 0 || num_partitions == 0) return GLU_OK;
-    sort->last_batch[path - 1] = (uint32_t) num_partitions;
+    sort->last_batch.by_class[path - 1] = (uint32_t) num_partitions;
     hipStream_t st = pick_stream(stream);
     if (path == 3)
     {
@@ -294,11 +265,9 @@ glu_status glu_radix_sort_run_batch_offsets_ptr(glu_radix_sort sort, void* keys,
     GLU_TRY(enter());
     if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
     GLU_TRY(check_arrays(keys, vals, total, key_type));
-    if (num_segments > kBatchMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %zu exceeds 2^24", num_segments);
-    if (num_segments && !offsets) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid offsets array");
-    if ((uintptr_t) offsets % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the offsets array is not aligned to its element size");
-    sort->last_batch_on_device = false;
-    sort->last_batch[0] = sort->last_batch[1] = sort->last_batch[2] = 0;
+    GLU_TRY(check_batch_segments(num_segments));
+    GLU_TRY(check_batch_offsets(offsets, num_segments));
+    sort->last_batch.reset();
     if (num_segments == 0 || total < 2) return GLU_OK; // (no segment can hold two elements)
     hipStream_t st = pick_stream(stream);
     const uint32_t xf = transform_of(key_type);
@@ -313,19 +282,7 @@ glu_status glu_radix_sort_read_batch(glu_radix_sort sort, uint32_t* wave_segment
 {
     GLU_TRY(enter());
     if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    uint32_t by_class[3] = {sort->last_batch[0], sort->last_batch[1], sort->last_batch[2]};
-    if (sort->last_batch_on_device)
-    {
-        uint32_t counts[kBatchLists];
-        HIP_TRY(hipMemcpy(counts, sort->batch_lists.ptr, sizeof(counts), hipMemcpyDeviceToHost));
-        by_class[0] = counts[0];
-        by_class[1] = counts[1] + counts[2] + counts[3];
-        by_class[2] = counts[4];
-    }
-    if (wave_segments) *wave_segments = by_class[0];
-    if (block_segments) *block_segments = by_class[1];
-    if (long_segments) *long_segments = by_class[2];
-    return GLU_OK;
+    return sort->last_batch.read(sort->batch_lists, 1, wave_segments, block_segments, long_segments); // (list 0: the wave class)
 }
 
 } // extern "C"

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "glu_host.hpp"
+#include "glu_batch_host.hpp"
 #include "radix_sort_kernels.hpp"
 
 namespace glu_hip
@@ -113,8 +113,7 @@ struct glu_radix_sort_s
     bool last_planned = false; // the last sort on this object ran with a device-side plan (glu_radix_sort_read_plan)
     // the batched sort (glu_sort_batch.hip): the list counts and the five lists of segment indices its binning kernel writes
     Scratch batch_lists;
-    uint32_t last_batch[3] = {};       // segments per class (wave, workgroup, long) of the last batched call, where the host chose
-    bool last_batch_on_device = false; // ... the device did: glu_radix_sort_read_batch reads the list counts
+    LastBatch last_batch; // segments per class of the last batched call (glu_radix_sort_read_batch)
     // pinned host images of the descriptors, a ring: a call fills the next one and enqueues its copy; an image is reused
     // only after the copy enqueued from it has run (its event)
     struct SegStage

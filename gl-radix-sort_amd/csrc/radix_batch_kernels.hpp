@@ -12,10 +12,12 @@
 //   long   radix_batch_long_kernel   any length: one workgroup per segment streams 8-bit counting passes (the reference's stable
 //                                    counting pass, RadixSort.hpp:142-182, by one workgroup) between the caller's arrays and the
 //                                    object's scratch arrays; an even number of passes, so the result lands in the caller's arrays.
-// radix_batch_bin_kernel in front (device offsets only) writes the five lists.  A segment is [offsets[s], offsets[s + 1]); one
-// whose end lies below its begin or beyond `total` is EMPTY to every kernel here (batch_segment: the bounds clamp).
+// radix_batch_bin_kernel in front (device offsets only) writes the five lists.  The lists, their layout and the clamps are
+// batch_lists.hpp's: a segment is [offsets[s], offsets[s + 1]), and one whose end lies below its begin or beyond `total` is EMPTY
+// to every kernel here (batch_offsets_segment).
 #pragma once
 
+#include "batch_lists.hpp"
 #include "radix_sort_kernels.hpp"
 
 namespace glu_hip
@@ -23,36 +25,20 @@ namespace glu_hip
 constexpr int kBatchWaveKpt = 8;                                // elements per lane of the wave class
 constexpr uint32_t kBatchWaveTile = kWave * kBatchWaveKpt;      // 512
 constexpr int kBatchWaveWaves = 4;                              // waves (= segments in flight) per workgroup of the wave class
-constexpr int kBatchLists = 5;                                  // wave, block x 3 tile geometries, long
+constexpr int kBatchLists = BATCH_LIST_LONG + 1;                // wave, block x 3 tile geometries, long: one-word entries, no chunks
 constexpr int kBatchLongKpt = 4;                                // elements per thread and tile of the long class (1024 threads)
 
 // Element range of segment `seg`.  offsets == NULL: equal partitions of `count` elements (the host checked count x partitions
-// against 2^32).  Device offsets cannot be checked by the host: a segment that ends below its begin or beyond `total` is empty,
-// so no kernel reads or writes outside [0, total) whatever the array holds.
+// against 2^32).
 __device__ __forceinline__ void batch_segment(const uint32_t* __restrict__ offsets, uint32_t count, uint32_t total, uint32_t seg,
                                               uint32_t& begin, uint32_t& len)
 {
-    if (offsets)
-    {
-        const uint32_t b = offsets[seg];
-        uint32_t e = offsets[seg + 1];
-        if (e < b || e > total) e = b;
-        begin = b;
-        len = e - b;
-    }
+    if (offsets) batch_offsets_segment(offsets, total, seg, begin, len);
     else
     {
         begin = seg * count;
         len = count;
     }
-}
-
-// How many entries of a list a kernel walks: the count the binning kernel wrote, never more than the list holds.
-__device__ __forceinline__ uint32_t batch_list_length(const uint32_t* __restrict__ list_count, uint32_t capacity)
-{
-    if (!list_count) return capacity;
-    const uint32_t n = *list_count;
-    return n < capacity ? n : capacity;
 }
 
 // Stable rank of this lane's element among the elements of the wave that were ranked into `row` so far and share its digit `d`
@@ -90,18 +76,11 @@ __device__ __forceinline__ void batch_wave_sync()
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Binning (device offsets): list c receives the indices of the segments of class c, counts[c] their number.  Wave-aggregated
-// appends: one vector atomic per wave and class.  Order inside a list does not matter.  Segments of 0 or 1 elements are in no list.
+// Binning (device offsets): list c receives the indices of the segments of class c, its word of the count line their number
+// (batch_append).  Segments of 0 or 1 elements are in no list.
 // ---------------------------------------------------------------------------------------------------------
-struct BatchLists
-{
-    uint32_t start[kBatchLists];    // first word of list c in `lists` (which lie behind the counts, not over them)
-    uint32_t capacity[kBatchLists]; // entries list c holds (the most segments of its class that fit `total`)
-    uint32_t limit[kBatchLists];    // longest segment of class c (the last one: no limit)
-};
-
 __global__ __launch_bounds__(256) void radix_batch_bin_kernel(const uint32_t* __restrict__ offsets, uint32_t nsegs, uint32_t total,
-                                                              BatchLists layout, uint32_t* __restrict__ counts,
+                                                              BatchListsLayout layout, uint32_t* __restrict__ counts,
                                                               uint32_t* __restrict__ lists)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -112,30 +91,16 @@ __global__ __launch_bounds__(256) void radix_batch_bin_kernel(const uint32_t* __
         if (seg < nsegs)
         {
             uint32_t begin, len;
-            batch_segment(offsets, 0u, total, seg, begin, len);
+            batch_offsets_segment(offsets, total, seg, begin, len);
             if (len >= 2u)
             {
-                cls = kBatchLists - 1;
+                cls = BATCH_LIST_LONG;
 #pragma unroll
-                for (int c = kBatchLists - 2; c >= 0; c--)
+                for (int c = BATCH_LIST_BLOCK; c >= 0; c--)
                     if (len <= layout.limit[c]) cls = c;
             }
         }
-#pragma unroll
-        for (int c = 0; c < kBatchLists; c++)
-        {
-            const uint64_t m = __ballot(cls == c);
-            if (m == 0) continue; // wave-uniform
-            const int leader = __ffsll((unsigned long long) m) - 1;
-            uint32_t first = 0;
-            if ((int) lane == leader) first = atomicAdd(&counts[c], (uint32_t) __popcll(m));
-            first = (uint32_t) __shfl((int) first, leader);
-            if (cls == c)
-            {
-                const uint32_t at = first + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
-                if (at < layout.capacity[c]) lists[layout.start[c] + at] = seg; // (cannot overflow with non-decreasing offsets)
-            }
-        }
+        batch_append<kBatchLists>(cls, seg, lane, layout, counts, lists);
     }
 }
 
@@ -164,7 +129,7 @@ __global__ __launch_bounds__(kBatchWaveWaves* kWave) void radix_batch_wave_kerne
     uint32_t* const row = s.cnt[wave];
     uint4* const row4 = reinterpret_cast<uint4*>(row);
     const KeyCodec<KeyT, true> codec(xf);
-    const uint32_t n_list = batch_list_length(list_count, nsegs);
+    const uint32_t n_list = list_count ? batch_list_length(*list_count, nsegs) : nsegs;
 
     for (uint32_t li = blockIdx.x * kBatchWaveWaves + wave; li < n_list; li += gridDim.x * kBatchWaveWaves)
     {
@@ -261,7 +226,7 @@ __global__ __launch_bounds__(THREADS) void radix_batch_block_kernel(KeyT* __rest
     const uint32_t wave_off = wave * WAVE_TILE + lane;
     uint32_t* const my_cnt = s.wcnt[wave];
     const KeyCodec<KeyT, true> codec(xf);
-    const uint32_t n_list = batch_list_length(list_count, nsegs);
+    const uint32_t n_list = list_count ? batch_list_length(*list_count, nsegs) : nsegs;
 
     for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x)
     {
@@ -377,7 +342,7 @@ __global__ __launch_bounds__(1024) void radix_batch_long_kernel(KeyT* __restrict
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t* const my_cnt = s.wcnt[wave];
     const KeyCodec<KeyT, true> codec(xf);
-    const uint32_t n_list = batch_list_length(list_count, nsegs);
+    const uint32_t n_list = list_count ? batch_list_length(*list_count, nsegs) : nsegs;
 
     for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x)
     {

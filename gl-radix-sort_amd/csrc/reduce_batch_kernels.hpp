@@ -13,8 +13,9 @@
 //                                       partials[its slot]; reduce_batch_block_kernel in COMBINE mode then folds every long
 //                                       segment's partials, which lie side by side in chunk order.
 // reduce_batch_bin_kernel in front (device offsets only) writes the identity of empty segments and the lists: three short lists,
-// the medium list, the long list and the list of chunks.  A segment is [offsets[s], offsets[s + 1]); one whose end lies below its
-// begin or beyond `total` is EMPTY to every kernel here (reduce_batch_segment), so nothing outside [0, total) is ever read.
+// the medium list, the long list and the list of chunks.  The lists, their layout and the clamps are batch_lists.hpp's: a segment
+// is [offsets[s], offsets[s + 1]), and one whose end lies below its begin or beyond `total` is EMPTY to every kernel here
+// (batch_offsets_segment), so nothing outside [0, total) is ever read.
 //
 // Order of combination: a lane folds its elements in ascending order, groups / waves / workgroups combine in lane, wave and chunk
 // order.  Which element goes to which lane depends on the segment's address (the 16-byte alignment), its length and nothing else:
@@ -22,6 +23,7 @@
 // segment are adjacent and ordered).  No identity is needed inside the folds (the `has` flags of block_reduce).
 #pragma once
 
+#include "batch_lists.hpp"
 #include "scan_reduce_kernels.hpp"
 
 namespace glu_hip
@@ -34,20 +36,6 @@ constexpr uint32_t kRbGroup16Elems = 64;        // up to here 16 lanes, beyond i
 constexpr int kRbThreads = 256;
 constexpr int kRbWaves = kRbThreads / kW;
 constexpr int kRbUnroll = 4;                    // loads in flight per lane
-
-enum
-{
-    RB_LIST_SHORT4 = 0,
-    RB_LIST_SHORT16 = 1,
-    RB_LIST_SHORT64 = 2,
-    RB_LIST_BLOCK = 3,
-    RB_LIST_LONG = 4,   // uint2 entries: segment, slot of its first chunk
-    RB_LIST_CHUNKS = 5, // uint2 entries: segment, chunk of the segment
-    RB_LISTS = 6
-};
-// counts[0 .. 3]: lengths of the four segment lists; counts[4 .. 5]: chunk slots handed out, ONE 64-bit counter (overlapping long
-// segments -- malformed offsets only -- can ask for far more than 2^32 of them, and it must not wrap); counts[6]: long segments.
-constexpr int kRbCountChunks = 4, kRbCountLong = 6, kRbCounts = 7;
 
 // host only: class (0 = empty, 1 = short, 2 = medium, 3 = long) and workgroups one segment of `count` elements is spread over
 inline void reduce_batch_plan(uint64_t count, uint32_t elem_bytes, uint32_t& path, uint32_t& workgroups)
@@ -65,25 +53,18 @@ inline void reduce_batch_plan(uint64_t count, uint32_t elem_bytes, uint32_t& pat
     }
 }
 
-struct ReduceBatchLayout
-{
-    uint32_t start[RB_LISTS];    // first word of list c behind the counts
-    uint32_t capacity[RB_LISTS]; // entries list c holds
-    uint32_t limit[4];           // longest segment (elements) of the four segment lists; longer ones are long
-    uint32_t chunk;              // elements of a chunk
-};
-
-struct ReduceBatchArgs
+// what the kernels that walk the six lists (the reduce's and the scan's) are told about a call
+struct BatchListsArgs
 {
     const uint32_t* offsets; // device offsets, or NULL: equal partitions of `count` elements
     uint64_t count;
     uint32_t total;          // device offsets: elements of the array
     uint32_t nsegs;          // segments / partitions
     uint32_t chunks_per;     // equal partitions of the long class: chunks of one partition
-    int sub;                 // equal partitions of the short class: which group size (RB_LIST_SHORT*)
+    int sub;                 // equal partitions of the short class: which group size (BATCH_LIST_SHORT*)
     const uint32_t* counts;  // device offsets: the list counts and the lists
     const uint32_t* lists;
-    ReduceBatchLayout layout;
+    BatchListsLayout layout;
 };
 
 struct ReduceBatchIdentity
@@ -92,16 +73,9 @@ struct ReduceBatchIdentity
 };
 
 // Element range of segment `seg` (see the head of the file for malformed offsets).
-__device__ __forceinline__ void reduce_batch_segment(const ReduceBatchArgs& a, uint32_t seg, uint64_t& begin, uint64_t& len)
+__device__ __forceinline__ void batch_lists_segment(const BatchListsArgs& a, uint32_t seg, uint64_t& begin, uint64_t& len)
 {
-    if (a.offsets)
-    {
-        const uint32_t b = a.offsets[seg];
-        uint32_t e = a.offsets[seg + 1];
-        if (e < b || e > a.total) e = b;
-        begin = b;
-        len = e - b;
-    }
+    if (a.offsets) batch_offsets_segment(a.offsets, a.total, seg, begin, len);
     else
     {
         begin = (uint64_t) seg * a.count;
@@ -109,20 +83,12 @@ __device__ __forceinline__ void reduce_batch_segment(const ReduceBatchArgs& a, u
     }
 }
 
-// entries of list c a kernel walks: what the binning kernel counted, never more than the list holds
-__device__ __forceinline__ uint32_t reduce_batch_list_length(const ReduceBatchArgs& a, int c)
-{
-    const uint64_t n = c == RB_LIST_CHUNKS ? *reinterpret_cast<const unsigned long long*>(a.counts + kRbCountChunks)
-                                           : (uint64_t) a.counts[c == RB_LIST_LONG ? kRbCountLong : c];
-    return n < a.layout.capacity[c] ? (uint32_t) n : a.layout.capacity[c];
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Binning (device offsets; `static`, as `inline` is ignored on a kernel: the batched scan's translation unit includes this header too and bins with the same kernel,
 // elem_words = 0 and no `out`).  Empty segments get the identity here; every other segment is appended to the list of its class
 // (wave-aggregated: one atomic per wave and list), a long one also with one entry per chunk, written by the whole wave.
 // ---------------------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatchArgs a, uint32_t* __restrict__ counts, uint32_t* __restrict__ lists,
+static __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(BatchListsArgs a, uint32_t* __restrict__ counts, uint32_t* __restrict__ lists,
                                                                uint32_t* __restrict__ out, uint32_t elem_words, ReduceBatchIdentity identity)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -134,55 +100,41 @@ static __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatc
         if (seg < a.nsegs)
         {
             uint64_t begin, len;
-            reduce_batch_segment(a, seg, begin, len);
+            batch_lists_segment(a, seg, begin, len);
             if (len == 0)
             {
                 for (uint32_t w = 0; w < elem_words; w++) out[(size_t) seg * elem_words + w] = identity.w[w];
             }
             else
             {
-                cls = RB_LIST_LONG;
+                cls = BATCH_LIST_LONG;
 #pragma unroll
-                for (int c = RB_LIST_BLOCK; c >= 0; c--)
+                for (int c = BATCH_LIST_BLOCK; c >= 0; c--)
                     if (len <= a.layout.limit[c]) cls = c;
-                if (cls == RB_LIST_LONG) nchunks = (uint32_t) ((len + a.layout.chunk - 1) / a.layout.chunk);
+                if (cls == BATCH_LIST_LONG) nchunks = (uint32_t) ((len + a.layout.chunk - 1) / a.layout.chunk);
             }
         }
-#pragma unroll
-        for (int c = 0; c <= RB_LIST_BLOCK; c++)
-        {
-            const uint64_t m = __ballot(cls == c);
-            if (m == 0) continue; // wave-uniform
-            const int leader = __ffsll((unsigned long long) m) - 1;
-            uint32_t first = 0;
-            if ((int) lane == leader) first = atomicAdd(&counts[c], (uint32_t) __popcll(m));
-            first = (uint32_t) __shfl((int) first, leader);
-            if (cls == c)
-            {
-                const uint32_t at = first + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
-                if (at < a.layout.capacity[c]) lists[a.layout.start[c] + at] = seg; // (cannot overflow with non-decreasing offsets)
-            }
-        }
+        batch_append<BATCH_LIST_LONG>(cls, seg, lane, a.layout, counts, lists);
         // Long segments are few (each is longer than a chunk): atomics of its own for each.  First its run of chunk slots; its
         // place in the long list only if the whole run lies inside the chunk list, so that every listed segment has all its
         // partials.  (Non-decreasing offsets always fit; of overlapping segments those that do not get no result.)
-        uint32_t slot = a.layout.capacity[RB_LIST_CHUNKS];
-        if (cls == RB_LIST_LONG)
+        uint32_t slot = a.layout.capacity[BATCH_LIST_CHUNKS];
+        if (cls == BATCH_LIST_LONG)
         {
-            const unsigned long long got = atomicAdd(reinterpret_cast<unsigned long long*>(counts + kRbCountChunks), (unsigned long long) nchunks);
-            if (got < a.layout.capacity[RB_LIST_CHUNKS]) slot = (uint32_t) got;
-            if (got + nchunks <= a.layout.capacity[RB_LIST_CHUNKS])
+            const unsigned long long got = atomicAdd(reinterpret_cast<unsigned long long*>(counts + kBatchCountChunks), (unsigned long long) nchunks);
+            if (got < a.layout.capacity[BATCH_LIST_CHUNKS]) slot = (uint32_t) got;
+            if (got + nchunks <= a.layout.capacity[BATCH_LIST_CHUNKS])
             {
-                const uint32_t at = atomicAdd(&counts[kRbCountLong], 1u);
-                if (at < a.layout.capacity[RB_LIST_LONG])
+                const uint32_t at = atomicAdd(&counts[kBatchCountLong], 1u);
+                if (at < a.layout.capacity[BATCH_LIST_LONG])
                 {
-                    uint2* entry = reinterpret_cast<uint2*>(lists + a.layout.start[RB_LIST_LONG]) + at;
+                    uint2* entry = reinterpret_cast<uint2*>(lists + a.layout.start[BATCH_LIST_LONG]) + at;
                     *entry = make_uint2(seg, slot);
                 }
             }
         }
         // every slot below the chunk list's length gets its entry, also from a run that only begins inside the list
-        uint64_t m = __ballot(cls == RB_LIST_LONG);
+        uint64_t m = __ballot(cls == BATCH_LIST_LONG);
         while (m) // wave-uniform
         {
             const int src = __ffsll((unsigned long long) m) - 1;
@@ -190,9 +142,9 @@ static __global__ __launch_bounds__(256) void reduce_batch_bin_kernel(ReduceBatc
             const uint32_t s_seg = (uint32_t) __shfl((int) seg, src);
             const uint32_t s_slot = (uint32_t) __shfl((int) slot, src);
             const uint32_t s_n = (uint32_t) __shfl((int) nchunks, src);
-            uint2* chunks = reinterpret_cast<uint2*>(lists + a.layout.start[RB_LIST_CHUNKS]);
+            uint2* chunks = reinterpret_cast<uint2*>(lists + a.layout.start[BATCH_LIST_CHUNKS]);
             for (uint32_t c = lane; c < s_n; c += kW)
-                if ((uint64_t) s_slot + c < a.layout.capacity[RB_LIST_CHUNKS]) chunks[s_slot + c] = make_uint2(s_seg, c);
+                if ((uint64_t) s_slot + c < a.layout.capacity[BATCH_LIST_CHUNKS]) chunks[s_slot + c] = make_uint2(s_seg, c);
         }
     }
 }
@@ -210,7 +162,7 @@ static __global__ __launch_bounds__(256) void reduce_batch_fill_kernel(uint32_t*
 // ---------------------------------------------------------------------------------------------------------
 template<int OP, typename S, int N>
 __global__ __launch_bounds__(kRbThreads) void reduce_batch_wave_kernel(const Elem<S, N>* __restrict__ data, Elem<S, N>* __restrict__ out,
-                                                                        ReduceBatchArgs a)
+                                                                        BatchListsArgs a)
 {
     using T = Elem<S, N>;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -218,9 +170,9 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_wave_kernel(const Ele
     const int sub = a.lists ? (int) (blockIdx.x % 3u) : a.sub;
     const uint32_t block = a.lists ? blockIdx.x / 3u : blockIdx.x;
     const uint32_t blocks = a.lists ? gridDim.x / 3u : gridDim.x;
-    const uint32_t lg = sub == RB_LIST_SHORT4 ? 2u : sub == RB_LIST_SHORT16 ? 4u : 6u;
+    const uint32_t lg = sub == BATCH_LIST_SHORT4 ? 2u : sub == BATCH_LIST_SHORT16 ? 4u : 6u;
     const uint32_t G = 1u << lg, per_wave = kW >> lg;
-    const uint32_t n = a.lists ? reduce_batch_list_length(a, sub) : a.nsegs;
+    const uint32_t n = a.lists ? batch_list_length(a.counts, a.layout, sub) : a.nsegs;
     const uint32_t* list = a.lists ? a.lists + a.layout.start[sub] : nullptr;
     const uint32_t j = lane & (G - 1u);
 
@@ -232,7 +184,7 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_wave_kernel(const Ele
         if (li < n)
         {
             seg = list ? list[li] : (uint32_t) li;
-            reduce_batch_segment(a, seg, begin, len);
+            batch_lists_segment(a, seg, begin, len);
         }
         const T* p = data + begin;
         T acc = zero_elem<S, N>();
@@ -319,30 +271,30 @@ __device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __rest
 // ---------------------------------------------------------------------------------------------------------
 template<int OP, typename S, int N>
 __global__ __launch_bounds__(kRbThreads) void reduce_batch_block_kernel(const Elem<S, N>* __restrict__ src, Elem<S, N>* __restrict__ out,
-                                                                         ReduceBatchArgs a, int combine_partials)
+                                                                         BatchListsArgs a, int combine_partials)
 {
     using T = Elem<S, N>;
     __shared__ T wtmp[kRbWaves];
     __shared__ uint32_t whas[kRbWaves];
     const uint32_t tid = threadIdx.x;
-    const int c = combine_partials ? RB_LIST_LONG : RB_LIST_BLOCK;
-    const uint32_t n = a.lists ? reduce_batch_list_length(a, c) : a.nsegs;
+    const int c = combine_partials ? BATCH_LIST_LONG : BATCH_LIST_BLOCK;
+    const uint32_t n = a.lists ? batch_list_length(a.counts, a.layout, c) : a.nsegs;
     for (uint32_t li = blockIdx.x; li < n; li += gridDim.x)
     {
         uint32_t seg = li;
         uint64_t begin, len;
         if (!combine_partials)
         {
-            if (a.lists) seg = a.lists[a.layout.start[RB_LIST_BLOCK] + li];
-            reduce_batch_segment(a, seg, begin, len);
+            if (a.lists) seg = a.lists[a.layout.start[BATCH_LIST_BLOCK] + li];
+            batch_lists_segment(a, seg, begin, len);
         }
         else if (a.lists)
         {
-            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[RB_LIST_LONG])[li];
+            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[BATCH_LIST_LONG])[li];
             seg = entry.x;
             begin = entry.y;
             uint64_t sb, sl;
-            reduce_batch_segment(a, seg, sb, sl);
+            batch_lists_segment(a, seg, sb, sl);
             len = (sl + a.layout.chunk - 1) / a.layout.chunk; // (a listed segment's whole run lies inside the chunk list)
         }
         else
@@ -364,19 +316,19 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_block_kernel(const El
 // per (partition, chunk) pair.
 template<int OP, typename S, int N>
 __global__ __launch_bounds__(kRbThreads) void reduce_batch_chunk_kernel(const Elem<S, N>* __restrict__ data, Elem<S, N>* __restrict__ partials,
-                                                                         ReduceBatchArgs a, uint64_t nitems)
+                                                                         BatchListsArgs a, uint64_t nitems)
 {
     using T = Elem<S, N>;
     __shared__ T wtmp[kRbWaves];
     __shared__ uint32_t whas[kRbWaves];
     const uint32_t tid = threadIdx.x;
-    const uint64_t n = a.lists ? (uint64_t) reduce_batch_list_length(a, RB_LIST_CHUNKS) : nitems;
+    const uint64_t n = a.lists ? (uint64_t) batch_list_length(a.counts, a.layout, BATCH_LIST_CHUNKS) : nitems;
     for (uint64_t slot = blockIdx.x; slot < n; slot += gridDim.x)
     {
         uint32_t seg, chunk;
         if (a.lists)
         {
-            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[RB_LIST_CHUNKS])[slot];
+            const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[BATCH_LIST_CHUNKS])[slot];
             seg = entry.x;
             chunk = entry.y;
         }
@@ -386,7 +338,7 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_chunk_kernel(const El
             chunk = (uint32_t) (slot % a.chunks_per);
         }
         uint64_t begin, len;
-        reduce_batch_segment(a, seg, begin, len);
+        batch_lists_segment(a, seg, begin, len);
         const uint64_t at = (uint64_t) chunk * a.layout.chunk;
         T acc = zero_elem<S, N>();
         bool has = false;

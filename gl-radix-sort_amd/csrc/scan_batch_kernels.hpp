@@ -16,8 +16,8 @@
 //                                      its carry-in.  12 B per 4-byte element, and one long segment fills the device.
 // In front, the batched reduce's binning kernel (reduce_batch_bin_kernel, with no `out` array to write identities to) lists the
 // segments by class: three short lists by group size, the medium list, the long list and the list of chunks.  The lists, their
-// counts and the clamps are the batched reduce's (ReduceBatchLayout, reduce_batch_segment, reduce_batch_list_length): a segment
-// whose end lies below its begin or beyond `total` is EMPTY to every kernel, so nothing outside [0, total) is read or written.
+// layout and the clamps are batch_lists.hpp's (BatchListsLayout, batch_offsets_segment, batch_list_length): a segment whose end
+// lies below its begin or beyond `total` is EMPTY to every kernel, so nothing outside [0, total) is read or written.
 //
 // Order of addition: inside a lane in ascending order, then lanes, waves, tiles and chunks in their order.  Which element goes to
 // which lane depends on the segment's address (its 16-byte alignment), its length and its class, and on nothing else: no atomics
@@ -66,7 +66,7 @@ inline void scan_batch_plan(uint64_t count, uint32_t elem_bytes, uint32_t& path,
 // Short segments: a group of 1 << lg lanes per segment, the segment in registers.
 // ---------------------------------------------------------------------------------------------------------
 template<typename S, int N>
-__global__ __launch_bounds__(kSbThreads) void scan_batch_wave_kernel(Elem<S, N>* __restrict__ data, ReduceBatchArgs a)
+__global__ __launch_bounds__(kSbThreads) void scan_batch_wave_kernel(Elem<S, N>* __restrict__ data, BatchListsArgs a)
 {
     using T = Elem<S, N>;
     constexpr uint32_t EMAX = kSbWaveBytes / kW / (uint32_t) sizeof(T); // elements a lane can hold: 8 / 4 / 2 / 1
@@ -75,9 +75,9 @@ __global__ __launch_bounds__(kSbThreads) void scan_batch_wave_kernel(Elem<S, N>*
     // a third of the grid walks each short list
     const int sub = (int) (blockIdx.x % 3u);
     const uint32_t block = blockIdx.x / 3u, blocks = gridDim.x / 3u;
-    const uint32_t lg = sub == RB_LIST_SHORT4 ? 2u : sub == RB_LIST_SHORT16 ? 4u : 6u;
+    const uint32_t lg = sub == BATCH_LIST_SHORT4 ? 2u : sub == BATCH_LIST_SHORT16 ? 4u : 6u;
     const uint32_t G = 1u << lg, per_wave = kW >> lg;
-    const uint32_t n = reduce_batch_list_length(a, sub);
+    const uint32_t n = batch_list_length(a.counts, a.layout, sub);
     const uint32_t* list = a.lists + a.layout.start[sub];
     const uint32_t j = lane & (G - 1u);
 
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kSbThreads) void scan_batch_wave_kernel(Elem<S, N>*
     {
         const uint64_t li = first + (lane >> lg);
         uint64_t begin = 0, len64 = 0;
-        if (li < n) reduce_batch_segment(a, list[li], begin, len64);
+        if (li < n) batch_lists_segment(a, list[li], begin, len64);
         uint32_t len = (uint32_t) len64;
         if (len > a.layout.limit[sub]) len = 0; // (only overlapping -- malformed -- lists can hold such an entry)
         T* p = data + begin;
@@ -220,30 +220,30 @@ __device__ __forceinline__ void scan_batch_range(Elem<S, N>* __restrict__ p, uin
 // ---------------------------------------------------------------------------------------------------------
 template<typename S, int N>
 __global__ __launch_bounds__(kSbThreads) void scan_batch_block_kernel(Elem<S, N>* __restrict__ data, Elem<S, N>* __restrict__ partials,
-                                                                       ReduceBatchArgs a, int mode)
+                                                                       BatchListsArgs a, int mode)
 {
     using T = Elem<S, N>;
     __shared__ T wsum[2][kSbWaves];
     const uint32_t tid = threadIdx.x;
-    const int c = mode == SB_MODE_SEGMENTS ? RB_LIST_BLOCK : mode == SB_MODE_PARTIALS ? RB_LIST_LONG : RB_LIST_CHUNKS;
-    const uint32_t n = reduce_batch_list_length(a, c);
+    const int c = mode == SB_MODE_SEGMENTS ? BATCH_LIST_BLOCK : mode == SB_MODE_PARTIALS ? BATCH_LIST_LONG : BATCH_LIST_CHUNKS;
+    const uint32_t n = batch_list_length(a.counts, a.layout, c);
     uint32_t phase = 0;
     for (uint32_t li = blockIdx.x; li < n; li += gridDim.x)
     {
         uint64_t begin, len;
         if (mode == SB_MODE_SEGMENTS)
         {
-            reduce_batch_segment(a, a.lists[a.layout.start[RB_LIST_BLOCK] + li], begin, len);
+            batch_lists_segment(a, a.lists[a.layout.start[BATCH_LIST_BLOCK] + li], begin, len);
             scan_batch_range<S, N>(data + begin, (uint32_t) len, zero_elem<S, N>(), tid, wsum, phase);
             continue;
         }
         const uint2 entry = reinterpret_cast<const uint2*>(a.lists + a.layout.start[c])[li];
-        reduce_batch_segment(a, entry.x, begin, len);
+        batch_lists_segment(a, entry.x, begin, len);
         if (mode == SB_MODE_PARTIALS)
         {
             // entry.y = slot of the segment's first chunk (a listed segment's whole run lies inside the chunk list)
             const uint64_t nchunks = (len + a.layout.chunk - 1) / a.layout.chunk;
-            uint64_t room = a.layout.capacity[RB_LIST_CHUNKS] > entry.y ? a.layout.capacity[RB_LIST_CHUNKS] - entry.y : 0;
+            uint64_t room = a.layout.capacity[BATCH_LIST_CHUNKS] > entry.y ? a.layout.capacity[BATCH_LIST_CHUNKS] - entry.y : 0;
             scan_batch_range<S, N, true>(partials + entry.y, (uint32_t) (nchunks < room ? nchunks : room), zero_elem<S, N>(), tid, wsum, phase);
         }
         else

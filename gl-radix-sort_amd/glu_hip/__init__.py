@@ -286,6 +286,12 @@ def plan_scan_batch(count, elem_bytes=4):
     return a.value, b.value
 
 
+def _read_batch(fn, handle):
+    a, b, c = _u32(0), _u32(0), _u32(0)
+    check(fn(handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return {"wave": a.value, "block": b.value, "long": c.value}
+
+
 class RadixSort:
     """glu::RadixSort (reference glu/RadixSort.hpp:186-354) over the C ABI."""
 
@@ -414,9 +420,7 @@ class RadixSort:
 
     def read_batch(self):
         """{wave, block, long}: segments each path of the last batched call took (glu_radix_sort_read_batch); synchronise first."""
-        a, b, c = _u32(0), _u32(0), _u32(0)
-        check(lib().glu_radix_sort_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return {"wave": a.value, "block": b.value, "long": c.value}
+        return _read_batch(lib().glu_radix_sort_read_batch, self._h)
 
     def sort_bit_range_ptr(self, keys_ptr, vals_ptr, count, begin_bit, end_bit, stream=None, key_bytes=4):
         """Stable sort by the key bits [begin_bit, end_bit) only; vals_ptr may be None (keys only)."""
@@ -488,9 +492,7 @@ class BlellochScan:
 
     def read_batch(self):
         """{wave, block, long}: segments each path of the last batched call took (glu_scan_read_batch); synchronise first."""
-        a, b, c = _u32(0), _u32(0), _u32(0)
-        check(lib().glu_scan_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return {"wave": a.value, "block": b.value, "long": c.value}
+        return _read_batch(lib().glu_scan_read_batch, self._h)
 
     def destroy(self):
         if self._h and _lib is not None:
@@ -536,9 +538,7 @@ class Reduce:
 
     def read_batch(self):
         """{wave, block, long}: segments each path of the last batched call took (glu_reduce_read_batch); synchronise first."""
-        a, b, c = _u32(0), _u32(0), _u32(0)
-        check(lib().glu_reduce_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return {"wave": a.value, "block": b.value, "long": c.value}
+        return _read_batch(lib().glu_reduce_read_batch, self._h)
 
     def destroy(self):
         if self._h and _lib is not None:
