@@ -2,6 +2,7 @@
 #ifndef GLU_BLELLOCHSCAN_HPP
 #define GLU_BLELLOCHSCAN_HPP
 
+#include "KeyRuns.hpp"
 #include "data_types.hpp"
 #include "hip_utils.hpp"
 
@@ -49,6 +50,15 @@ namespace glu
         void scan_batch_offsets(void* device_data, size_t total, const uint32_t* device_offsets, size_t num_segments, void* stream = nullptr)
         {
             GLU_CHECK_STATUS(glu_scan_run_batch_offsets_ptr(m_impl, device_data, total, device_offsets, num_segments, stream));
+        }
+        /// Scan by key (KeyRuns.hpp): the runs of `k.keys` taken by `runs`, then the values of every run replaced by their own
+        /// exclusive scan, in place -- the two calls, on the caller's stream, with nothing between them.  device_values: k.count
+        /// elements of the data type.
+        void scan_by_key(KeyRuns& runs, const KeyRunsArrays& k, void* device_values, void* stream = nullptr)
+        {
+            GLU_CHECK_ARGUMENT(k.max_runs <= ((size_t) 1 << 24), "scan_by_key: max_runs %zu exceeds 2^24", k.max_runs);
+            runs(k.keys, k.count, k.key_bits, k.begin_bit, k.end_bit, k.unique_keys, k.offsets, k.max_runs, k.num_runs, stream);
+            scan_batch_offsets(device_values, k.count, k.offsets, k.max_runs, stream);
         }
         /// Scratch for batched scans of up to `total` elements in up to `num_segments` segments (they then allocate nothing and
         /// can be captured into a graph).

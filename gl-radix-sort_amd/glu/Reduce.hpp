@@ -2,6 +2,7 @@
 #ifndef GLU_REDUCE_HPP
 #define GLU_REDUCE_HPP
 
+#include "KeyRuns.hpp"
 #include "data_types.hpp"
 #include "hip_utils.hpp"
 
@@ -62,6 +63,15 @@ namespace glu
                                   size_t num_segments, void* stream = nullptr)
         {
             GLU_CHECK_STATUS(glu_reduce_run_batch_offsets_ptr(m_impl, device_data, device_out, total, device_offsets, num_segments, stream));
+        }
+        /// Reduce by key (KeyRuns.hpp): the runs of `k.keys` taken by `runs`, then device_out[r] = the reduction of the values of
+        /// run r, for r < k.max_runs (the operator's identity from the number of runs on) -- the two calls, on the caller's
+        /// stream, with nothing between them.  device_values: k.count elements of the data type, only read.
+        void reduce_by_key(KeyRuns& runs, const KeyRunsArrays& k, const void* device_values, void* device_out, void* stream = nullptr)
+        {
+            GLU_CHECK_ARGUMENT(k.max_runs <= ((size_t) 1 << 24), "reduce_by_key: max_runs %zu exceeds 2^24", k.max_runs);
+            runs(k.keys, k.count, k.key_bits, k.begin_bit, k.end_bit, k.unique_keys, k.offsets, k.max_runs, k.num_runs, stream);
+            reduce_batch_offsets(device_values, device_out, k.count, k.offsets, k.max_runs, stream);
         }
         /// Scratch for batched reduces of up to `total` elements in up to `num_segments` segments (they then allocate nothing and
         /// can be captured into a graph).

@@ -100,6 +100,11 @@ SYMBOLS = [
     ("glu_reduce_prepare_batch", _int, [_vp, _sz, _sz]),
     ("glu_reduce_plan_batch", _int, [_sz, _u32, _P(_u32), _P(_u32)]),
     ("glu_reduce_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_key_runs_create", _int, [_P(_vp)]),
+    ("glu_key_runs_destroy", _int, [_vp]),
+    ("glu_key_runs_prepare", _int, [_vp, _sz, _u32]),
+    ("glu_key_runs_run_ptr", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _vp]),
+    ("glu_key_runs_plan", _int, [_sz, _u32, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -286,6 +291,14 @@ def plan_scan_batch(count, elem_bytes=4):
     return a.value, b.value
 
 
+def plan_key_runs(count, key_bits=32):
+    """(tile, tiles, scan_rounds) of key runs over `count` keys of `key_bits` bits (glu_key_runs_plan; host only): keys per tile,
+    tiles of keys that start on a 16-byte boundary, rounds of the scan of the tile counts."""
+    a, b, c = _u32(0), _u32(0), _u32(0)
+    check(lib().glu_key_runs_plan(count, key_bits, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
+
+
 def _read_batch(fn, handle):
     a, b, c = _u32(0), _u32(0), _u32(0)
     check(fn(handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
@@ -462,6 +475,44 @@ class RadixSort:
             pass
 
 
+class KeyRuns:
+    """glu::KeyRuns (not in the reference) over the C ABI: the runs of equal keys as offsets for the batched calls."""
+
+    MAX_COMPOSED_RUNS = 1 << 24  # the limit of the batched calls, which run_by_key_ptr of Reduce and BlellochScan go through
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_key_runs_create(ctypes.byref(self._h)))
+
+    def prepare(self, count, key_bits=32):
+        """Scratch for up to `count` keys: after it run_ptr allocates nothing (capturable) (glu_key_runs_prepare)."""
+        check(lib().glu_key_runs_prepare(self._h, count, key_bits))
+
+    def run_ptr(self, keys_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr=None, key_bits=32, begin_bit=0,
+                end_bit=None, stream=None):
+        """offsets[0 .. max_runs] = the heads of the runs of keys equal in the bits [begin_bit, end_bit) (end_bit None: key_bits),
+        then `count`; unique_keys[r] = the key at head r (None skips it); *num_runs = the number of runs, also beyond max_runs.
+        All pointers are device pointers; the keys are only read (glu_key_runs_run_ptr)."""
+        check(lib().glu_key_runs_run_ptr(self._h, _vp(keys_ptr), count, key_bits, begin_bit, key_bits if end_bit is None else end_bit,
+                                         _vp(unique_keys_ptr), _vp(offsets_ptr), max_runs, _vp(num_runs_ptr), _vp(stream)))
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_key_runs_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _check_composed_runs(max_runs):
+    if max_runs > KeyRuns.MAX_COMPOSED_RUNS:
+        raise GluError(GLU_ERROR_INVALID_ARGUMENT, "max_runs %d exceeds 2^24" % max_runs)
+
+
 class BlellochScan:
     """glu::BlellochScan (reference glu/BlellochScan.hpp:80-191) over the C ABI."""
 
@@ -484,6 +535,14 @@ class BlellochScan:
         """Elements [offsets[s], offsets[s+1]) become their own exclusive scan, in place, for every segment (offsets: num_segments
         + 1 uint32 on the DEVICE) (glu_scan_run_batch_offsets_ptr)."""
         check(lib().glu_scan_run_batch_offsets_ptr(self._h, _vp(data_ptr), total, _vp(offsets_ptr), num_segments, _vp(stream)))
+
+    def run_by_key_ptr(self, runs, keys_ptr, values_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr=None,
+                       key_bits=32, begin_bit=0, end_bit=None, stream=None):
+        """Scan by key: runs.run_ptr on the keys, then the values of every run become their own exclusive scan, in place -- the
+        two calls on one stream (glu::BlellochScan::scan_by_key).  max_runs <= 2^24."""
+        _check_composed_runs(max_runs)
+        runs.run_ptr(keys_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr, key_bits, begin_bit, end_bit, stream)
+        self.run_batch_offsets_ptr(values_ptr, count, offsets_ptr, max_runs, stream)
 
     def prepare_batch(self, total, num_segments):
         """Grow-only scratch for batched scans of up to `total` elements in up to `num_segments` segments: after it the call
@@ -530,6 +589,14 @@ class Reduce:
         only read (glu_reduce_run_batch_offsets_ptr)."""
         check(lib().glu_reduce_run_batch_offsets_ptr(self._h, _vp(data_ptr), _vp(out_ptr), total, _vp(offsets_ptr), num_segments,
                                                      _vp(stream)))
+
+    def run_by_key_ptr(self, runs, keys_ptr, values_ptr, out_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr=None,
+                       key_bits=32, begin_bit=0, end_bit=None, stream=None):
+        """Reduce by key: runs.run_ptr on the keys, then out[r] = the reduction of the values of run r for r < max_runs (the
+        identity from the number of runs on) -- the two calls on one stream (glu::Reduce::reduce_by_key).  max_runs <= 2^24."""
+        _check_composed_runs(max_runs)
+        runs.run_ptr(keys_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr, key_bits, begin_bit, end_bit, stream)
+        self.run_batch_offsets_ptr(values_ptr, out_ptr, count, offsets_ptr, max_runs, stream)
 
     def prepare_batch(self, total, num_segments):
         """Grow-only scratch for batched reduces of up to `total` elements in up to `num_segments` segments: after it the two

@@ -85,6 +85,7 @@ typedef unsigned int glu_buffer; /* replaces GLuint buffer names (glu/gl_utils.h
 typedef struct glu_radix_sort_s* glu_radix_sort;
 typedef struct glu_scan_s* glu_scan;
 typedef struct glu_reduce_s* glu_reduce;
+typedef struct glu_key_runs_s* glu_key_runs;
 typedef struct glu_timer_s* glu_timer;
 typedef struct glu_dist_s* glu_dist;
 
@@ -513,6 +514,52 @@ GLU_API glu_status glu_reduce_plan_batch(size_t count, uint32_t elem_bytes, uint
  * (empty ones take none).  Any pointer may be NULL. */
 GLU_API glu_status glu_reduce_read_batch(glu_reduce reduce, uint32_t* wave_segments, uint32_t* block_segments,
                                          uint32_t* long_segments);
+
+/* ---- key runs (not in the reference): the runs of equal keys of an array -- of SORTED keys: the groups -- as an offsets array
+ * in exactly the form the three batched calls above take, so that what follows a sort by key needs no trip to the host:
+ * reduce-by-key is glu_key_runs_run_ptr + glu_reduce_run_batch_offsets_ptr on the values, scan-by-key is glu_key_runs_run_ptr +
+ * glu_scan_run_batch_offsets_ptr, a sort by a second key inside every group is glu_key_runs_run_ptr +
+ * glu_radix_sort_run_batch_offsets_ptr.  Those compositions are two calls on one stream and have no entry point of their own
+ * (glu::Reduce::reduce_by_key and glu::BlellochScan::scan_by_key make them).
+ *   - A HEAD is an index i with i == 0 or ((keys[i] ^ keys[i-1]) & mask) != 0, where mask covers the key bits
+ *     [begin_bit, end_bit).  R = the number of heads, h_0 < h_1 < ... their indices.  Equality is on BITS, the equivalence of the
+ *     sort's total order for all six glu_key_type's: -0.0 and +0.0 are different keys, NaNs with different payloads are
+ *     different keys; hence `key_bits` (32 or 64, as in glu_radix_sort_run_bit_range_ptr) and no key type.
+ *     begin_bit == end_bit: no bit tells keys apart, one run if count > 0.  The keys need not be sorted: unsorted keys simply
+ *     have more runs (the call is a run-length encoder).
+ *   - offsets (max_runs + 1 entries, EVERY one written): offsets[r] = h_r for r < min(R, max_runs), offsets[r] = count for
+ *     min(R, max_runs) <= r <= max_runs.  The array is non-decreasing, starts at 0 when count > 0 and ends at count: legal
+ *     offsets of max_runs segments for the batched calls, the segments behind the last run empty.  If R > max_runs the last
+ *     segment holds the remaining runs merged.
+ *   - unique_keys (optional, NULL skips it): unique_keys[r] = keys[h_r] for r < min(R, max_runs), the WHOLE key, not its masked
+ *     bits.  Entries behind that are not touched.
+ *   - *num_runs = R, the true number even where it exceeds max_runs: how a caller detects overflow (after synchronising, or on
+ *     the device).
+ *   - `keys` is READ ONLY.  count == 0: R = 0, every offset 0, NULL keys accepted.
+ *   - Limits: count < 2^32; max_runs < 2^32; keys and unique_keys aligned to the key size, offsets and num_runs to 4 bytes.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check: NULL runs; NULL keys with count > 0; NULL offsets or num_runs;
+ *     misalignment; key_bits other than 32 or 64; begin_bit > end_bit or end_bit > key_bits; the limits above; offsets,
+ *     unique_keys or num_runs overlapping keys.
+ *   - The call only enqueues on `stream`: no host synchronisation, no side stream, no read-back, and no device allocation once
+ *     glu_key_runs_prepare covered the count (else grow-only allocation inside the call: not capturable).  Always three
+ *     kernels, whose grids follow from count, max_runs and the address of keys, never from the data: the heads of every tile of
+ *     keys counted (glu_key_runs_plan: 256 threads x four 16-byte packs), the counts scanned by one workgroup with the tile loop
+ *     of the batched scan, the heads written at their ranks and the rest of offsets filled.  The keys are read twice; no
+ *     workgroup waits for another (no look-back, nothing in arrival order), so a captured call replays on any keys. */
+GLU_API glu_status glu_key_runs_create(glu_key_runs* out);
+GLU_API glu_status glu_key_runs_destroy(glu_key_runs runs);
+/* Grow-only scratch so that the call below allocates nothing (and can be captured) for up to `count` (< 2^32) keys of `key_bits`
+ * (32 or 64) bits: 4 bytes per tile of keys. */
+GLU_API glu_status glu_key_runs_prepare(glu_key_runs runs, size_t count, uint32_t key_bits);
+/* offsets[0 .. max_runs], unique_keys[0 .. min(R, max_runs)) and *num_runs as above; all four arrays on the DEVICE */
+GLU_API glu_status glu_key_runs_run_ptr(glu_key_runs runs, const void* keys, size_t count, uint32_t key_bits,
+                                        uint32_t begin_bit, uint32_t end_bit, void* unique_keys, uint32_t* offsets,
+                                        size_t max_runs, uint32_t* num_runs, void* stream);
+/* Host only, no device (unit-testable, like glu_scan_plan_batch): tile = keys per tile, tiles = ceil(count / tile), the tiles of
+ * `count` keys that start on a 16-byte boundary (tiles are counted from the boundary at or below `keys`: keys that start behind
+ * one can take one tile more), scan_rounds = the rounds the one workgroup that scans the tile counts makes (4096 counts each).
+ * Any pointer may be NULL. */
+GLU_API glu_status glu_key_runs_plan(size_t count, uint32_t key_bits, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
