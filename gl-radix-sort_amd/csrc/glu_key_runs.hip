@@ -71,8 +71,7 @@ glu_status run(const Call& c)
     hipLaunchKernelGGL((key_runs_count_kernel<K>), dim3(std::max(1u, std::min(a.tiles, device_grid))), dim3(kKrThreads), 0, c.stream, a,
                        tile_counts);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(key_runs_scan_kernel, dim3(1), dim3(kSbThreads), 0, c.stream, tile_counts, a.tiles, c.num_runs);
-    HIP_TRY(hipGetLastError());
+    GLU_TRY(launch_tile_count_scan(tile_counts, a.tiles, c.num_runs, c.stream));
     // (the fill: a workgroup per 4096 entries of offsets, if the tiles ask for fewer)
     const uint32_t fill_blocks = (uint32_t) std::min<uint64_t>((c.max_runs + 1 + 4095) / 4096, device_grid);
     hipLaunchKernelGGL((key_runs_write_kernel<K>), dim3(std::max(fill_blocks, std::min(a.tiles, device_grid))), dim3(kKrThreads), 0, c.stream,
@@ -81,6 +80,15 @@ glu_status run(const Call& c)
     return GLU_OK;
 }
 } // namespace
+
+glu_status glu_hip::host::launch_tile_count_scan(uint32_t* tile_counts, uint32_t tiles, uint32_t* total, hipStream_t stream)
+{
+    hipLaunchKernelGGL(key_runs_scan_kernel, dim3(1), dim3(kSbThreads), 0, stream, tile_counts, tiles, total);
+    HIP_TRY(hipGetLastError());
+    return GLU_OK;
+}
+
+uint32_t glu_hip::host::tile_count_scan_rounds(uint32_t tiles) { return (tiles + kKrScanRound - 1) / kKrScanRound; }
 
 extern "C" {
 

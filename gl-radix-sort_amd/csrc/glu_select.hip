@@ -1,0 +1,211 @@
+// glu_select.hip -- select of libglu_hip.so (select_kernels.hpp): glu_select_create, glu_select_destroy, glu_select_prepare,
+// glu_select_run_ptr, glu_select_plan.
+// The library's other translation units: glu_host.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "glu_batch_host.hpp"
+#include "glu_key_runs_object.hpp"
+#include "glu_select_object.hpp"
+#include "select_kernels.hpp"
+
+using namespace glu_hip;
+using namespace glu_hip::host;
+
+static_assert(GLU_SELECT_EQ == SELECT_EQ && GLU_SELECT_NE == SELECT_NE && GLU_SELECT_LT == SELECT_LT && GLU_SELECT_LE == SELECT_LE &&
+                  GLU_SELECT_GT == SELECT_GT && GLU_SELECT_GE == SELECT_GE && GLU_SELECT_OP_COUNT_ == SELECT_OPS_,
+              "the header's comparisons are the kernels'");
+
+namespace
+{
+glu_status check_count(size_t count)
+{
+    return count < ((size_t) 1 << 32) ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "select takes a count below 2^32 (got %zu)", count);
+}
+
+// bytes of a stencil element, 0 for what is no stencil type
+uint32_t stencil_bytes(int stencil_type)
+{
+    switch (stencil_type)
+    {
+    case GLU_DATA_TYPE_FLOAT:
+    case GLU_DATA_TYPE_INT:
+    case GLU_DATA_TYPE_UINT: return 4;
+    case GLU_DATA_TYPE_DOUBLE: return 8;
+    case GLU_SELECT_STENCIL_BYTE: return 1;
+    default: return 0;
+    }
+}
+
+glu_status check_stencil_type(int stencil_type)
+{
+    return stencil_bytes(stencil_type)
+               ? GLU_OK
+               : fail(GLU_ERROR_INVALID_ARGUMENT, "stencil_type must be FLOAT, DOUBLE, INT, UINT (0 .. 3) or GLU_SELECT_STENCIL_BYTE (12) (got %d)",
+                      stencil_type);
+}
+
+// The tile counts of `count` elements.  A base that is not 16-byte aligned moves the elements up to a pack's length into the first
+// tile, which can add a tile behind the last: one more than the plan's.
+glu_status reserve_tiles(glu_select_s* s, size_t count, int stencil_type)
+{
+    uint32_t tile, tiles;
+    select_plan(count, stencil_bytes(stencil_type), tile, tiles);
+    return count ? s->tile_counts.reserve(((size_t) tiles + 1) * sizeof(uint32_t)) : GLU_OK;
+}
+
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
+    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+struct Call
+{
+    glu_select_s* sel;
+    const void* stencil;
+    int op;
+    const void* threshold;
+    size_t count;
+    const void* items;
+    uint32_t item_bytes;
+    void* out_items;
+    uint32_t* out_indices;
+    size_t max_out;
+    uint32_t* num_selected;
+    hipStream_t stream;
+};
+
+template<typename S, uint32_t ITEM_BYTES>
+void launch_write(const Call& c, const SelectArgs<S>& a, const uint32_t* tile_counts, uint32_t grid)
+{
+    hipLaunchKernelGGL((select_write_kernel<S, ITEM_BYTES>), dim3(grid), dim3(kSelThreads), 0, c.stream, a, tile_counts, c.items, c.out_items,
+                       c.out_indices, (uint32_t) c.max_out);
+}
+
+// Three kernels, whatever the stencil holds: the selected elements of every tile counted, the counts scanned by one workgroup,
+// the selected elements written at their ranks.  The grids follow from `count` and the alignment of `stencil`, and whether the third
+// kernel is enqueued at all from the output pointers and `max_out`: never from the data.
+template<typename S>
+glu_status run(const Call& c)
+{
+    using C = SelectCfg<S>;
+    SelectArgs<S> a;
+    a.lo = ((uintptr_t) c.stencil & 15u) / sizeof(S);
+    a.hi = a.lo + c.count;
+    a.base = (const S*) c.stencil - a.lo;
+    S threshold = (S) 0; // (NULL: zero)
+    if (c.threshold) memcpy(&threshold, c.threshold, sizeof(S));
+    a.pred = make_select_pred<S>(c.op, threshold);
+    a.tiles = c.count ? (uint32_t) ((a.hi + C::TILE - 1) / C::TILE) : 0u;
+    uint32_t* tile_counts = (uint32_t*) c.sel->tile_counts.ptr;
+    const uint32_t grid = std::max(1u, std::min(a.tiles, cus() * 8u));
+    hipLaunchKernelGGL((select_count_kernel<S>), dim3(grid), dim3(kSelThreads), 0, c.stream, a, tile_counts);
+    HIP_TRY(hipGetLastError());
+    GLU_TRY(launch_tile_count_scan(tile_counts, a.tiles, c.num_selected, c.stream));
+    if (!a.tiles || !c.max_out || (!c.out_items && !c.out_indices)) return GLU_OK; // (nothing can be written: the call only counts)
+    switch (c.items ? c.item_bytes : 0u)
+    {
+    case 0: launch_write<S, 0>(c, a, tile_counts, grid); break;
+    case 4: launch_write<S, 4>(c, a, tile_counts, grid); break;
+    case 8: launch_write<S, 8>(c, a, tile_counts, grid); break;
+    case 16: launch_write<S, 16>(c, a, tile_counts, grid); break;
+    default: launch_write<S, 32>(c, a, tile_counts, grid); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return GLU_OK;
+}
+} // namespace
+
+extern "C" {
+
+glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds)
+{
+    GLU_TRY(check_stencil_type(stencil_type));
+    GLU_TRY(check_count(count));
+    uint32_t t, n;
+    select_plan(count, stencil_bytes(stencil_type), t, n);
+    if (tile) *tile = t;
+    if (tiles) *tiles = n;
+    if (scan_rounds) *scan_rounds = tile_count_scan_rounds(n);
+    return GLU_OK;
+}
+
+glu_status glu_select_create(glu_select* out)
+{
+    GLU_TRY(enter());
+    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
+    *out = new glu_select_s();
+    return GLU_OK;
+}
+
+glu_status glu_select_destroy(glu_select select)
+{
+    GLU_TRY(enter());
+    if (!select) return GLU_OK;
+    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
+    select->tile_counts.release();
+    delete select;
+    return GLU_OK;
+}
+
+glu_status glu_select_prepare(glu_select select, size_t count, int stencil_type)
+{
+    GLU_TRY(enter());
+    if (!select) return fail(GLU_ERROR_INVALID_ARGUMENT, "select is NULL");
+    GLU_TRY(check_stencil_type(stencil_type));
+    GLU_TRY(check_count(count));
+    return reserve_tiles(select, count, stencil_type);
+}
+
+glu_status glu_select_run_ptr(glu_select select, const void* stencil, int stencil_type, int op, const void* threshold, size_t count,
+                              const void* items, uint32_t item_bytes, void* out_items, uint32_t* out_indices, size_t max_out,
+                              uint32_t* num_selected, void* stream)
+{
+    GLU_TRY(enter());
+    if (!select) return fail(GLU_ERROR_INVALID_ARGUMENT, "select is NULL");
+    GLU_TRY(check_stencil_type(stencil_type));
+    if (op < 0 || op >= GLU_SELECT_OP_COUNT_) return fail(GLU_ERROR_INVALID_ARGUMENT, "op must be one of GLU_SELECT_EQ .. GLU_SELECT_GE (got %d)", op);
+    GLU_TRY(check_count(count));
+    if (max_out >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "max_out must be below 2^32 (got %zu)", max_out);
+    if (count && !stencil) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid stencil buffer");
+    if (!num_selected) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid num_selected pointer");
+    if (!items != !out_items) return fail(GLU_ERROR_INVALID_ARGUMENT, "items and out_items must both be given or both be NULL");
+    if (items && item_bytes != 4 && item_bytes != 8 && item_bytes != 16 && item_bytes != 32)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "item_bytes must be 4, 8, 16 or 32 (got %u)", item_bytes);
+    const size_t sb = stencil_bytes(stencil_type);
+    const size_t ib = items ? item_bytes : 0, item_align = std::min<size_t>(ib, 16);
+    if ((uintptr_t) stencil % sb) return fail(GLU_ERROR_INVALID_ARGUMENT, "stencil is not aligned to its element size");
+    if (items && (uintptr_t) items % item_align) return fail(GLU_ERROR_INVALID_ARGUMENT, "items is not aligned to min(item_bytes, 16)");
+    if (items && (uintptr_t) out_items % item_align) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_items is not aligned to min(item_bytes, 16)");
+    if ((uintptr_t) out_indices % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_indices is not aligned to 4 bytes");
+    if ((uintptr_t) num_selected % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_selected is not aligned to 4 bytes");
+    // (no more than min(count, max_out) entries of an output array can be written)
+    const size_t written = std::min(count, max_out);
+    const struct
+    {
+        const void* ptr;
+        size_t bytes;
+        const char* name;
+    } inputs[2] = {{stencil, count * sb, "stencil"}, {items, count * ib, "items"}},
+      outputs[3] = {{out_items, written * ib, "out_items"}, {out_indices, out_indices ? written * sizeof(uint32_t) : 0, "out_indices"},
+                    {num_selected, sizeof(uint32_t), "num_selected"}};
+    for (const auto& o : outputs)
+        for (const auto& i : inputs)
+            if (o.ptr && i.ptr && overlaps(i.ptr, i.bytes, o.ptr, o.bytes))
+                return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", o.name, i.name);
+    GLU_TRY(reserve_tiles(select, count, stencil_type));
+    const Call c{select, stencil, op, threshold, count, items, item_bytes, out_items, out_indices, max_out, num_selected, pick_stream(stream)};
+    switch (stencil_type)
+    {
+    case GLU_DATA_TYPE_FLOAT: return run<float>(c);
+    case GLU_DATA_TYPE_DOUBLE: return run<double>(c);
+    case GLU_DATA_TYPE_INT: return run<int32_t>(c);
+    case GLU_DATA_TYPE_UINT: return run<uint32_t>(c);
+    default: return run<uint8_t>(c);
+    }
+}
+
+} // extern "C"

@@ -17,6 +17,9 @@ LIB_PATH = os.environ.get("GLU_HIP_LIB_PATH") or os.path.join(_PKG_DIR, "lib", "
 DataType_Float, DataType_Double, DataType_Int, DataType_Uint, DataType_Vec2, DataType_Vec4, DataType_DVec2, \
     DataType_DVec4, DataType_UVec2, DataType_UVec4, DataType_IVec2, DataType_IVec4 = range(12)
 ReduceOperator_Sum, ReduceOperator_Mul, ReduceOperator_Min, ReduceOperator_Max = range(4)
+# glu_select_run_ptr: the stencil types (the four scalar data types with their values, and a byte) and the comparisons
+SelectStencil_Float, SelectStencil_Double, SelectStencil_Int, SelectStencil_Uint, SelectStencil_Byte = 0, 1, 2, 3, 12
+SelectOperator_EQ, SelectOperator_NE, SelectOperator_LT, SelectOperator_LE, SelectOperator_GT, SelectOperator_GE = range(6)
 
 GLU_OK = 0
 GLU_ERROR_INVALID_ARGUMENT = 1
@@ -105,6 +108,11 @@ SYMBOLS = [
     ("glu_key_runs_prepare", _int, [_vp, _sz, _u32]),
     ("glu_key_runs_run_ptr", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _vp]),
     ("glu_key_runs_plan", _int, [_sz, _u32, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_select_create", _int, [_P(_vp)]),
+    ("glu_select_destroy", _int, [_vp]),
+    ("glu_select_prepare", _int, [_vp, _sz, _int]),
+    ("glu_select_run_ptr", _int, [_vp, _vp, _int, _int, _vp, _sz, _vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    ("glu_select_plan", _int, [_sz, _int, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -296,6 +304,14 @@ def plan_key_runs(count, key_bits=32):
     tiles of keys that start on a 16-byte boundary, rounds of the scan of the tile counts."""
     a, b, c = _u32(0), _u32(0), _u32(0)
     check(lib().glu_key_runs_plan(count, key_bits, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
+
+
+def plan_select(count, stencil_type=SelectStencil_Uint):
+    """(tile, tiles, scan_rounds) of a select over `count` elements of a stencil of `stencil_type` (glu_select_plan; host only):
+    elements per tile, tiles of a stencil that starts on a 16-byte boundary, rounds of the scan of the tile counts."""
+    a, b, c = _u32(0), _u32(0), _u32(0)
+    check(lib().glu_select_plan(count, stencil_type, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
     return a.value, b.value, c.value
 
 
@@ -499,6 +515,52 @@ class KeyRuns:
     def destroy(self):
         if self._h and _lib is not None:
             _lib.glu_key_runs_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Select:
+    """glu::Select (not in the reference) over the C ABI: stable stream compaction by a stencil and a comparison."""
+
+    _THRESHOLD_TYPES = {SelectStencil_Float: ctypes.c_float, SelectStencil_Double: ctypes.c_double, SelectStencil_Int: ctypes.c_int32,
+                        SelectStencil_Uint: ctypes.c_uint32, SelectStencil_Byte: ctypes.c_uint8}
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_select_create(ctypes.byref(self._h)))
+
+    def prepare(self, count, stencil_type=SelectStencil_Uint):
+        """Scratch for up to `count` elements: after it run_ptr allocates nothing (capturable) (glu_select_prepare)."""
+        check(lib().glu_select_prepare(self._h, count, stencil_type))
+
+    def run_ptr(self, stencil_ptr, count, max_out, num_selected_ptr, out_indices_ptr=None, items_ptr=None, out_items_ptr=None,
+                item_bytes=4, stencil_type=SelectStencil_Uint, op=SelectOperator_NE, threshold=None, stream=None):
+        """Element i is selected iff stencil[i] `op` threshold (a Python number, packed into the stencil's type; None: zero).
+        out_indices[r] = the index of the r-th selected element, out_items[r] = its item (either may be None), for r below
+        min(selected, max_out); *num_selected = the number selected, also beyond max_out.  All pointers are device pointers; the
+        stencil and the items are only read (glu_select_run_ptr)."""
+        value = None
+        if threshold is not None and stencil_type in self._THRESHOLD_TYPES:
+            ctype = self._THRESHOLD_TYPES[stencil_type]
+            if ctype not in (ctypes.c_float, ctypes.c_double):
+                bits = 8 * ctypes.sizeof(ctype)
+                lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if ctype is ctypes.c_int32 else (0, (1 << bits) - 1)
+                if int(threshold) != threshold or not lo <= int(threshold) <= hi:
+                    raise GluError(GLU_ERROR_INVALID_ARGUMENT, "threshold %r is no value of the stencil's type" % (threshold,))
+                threshold = int(threshold)
+            value = ctype(threshold)
+        check(lib().glu_select_run_ptr(self._h, _vp(stencil_ptr), stencil_type, op, ctypes.byref(value) if value is not None else None, count,
+                                       _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr), max_out, _vp(num_selected_ptr),
+                                       _vp(stream)))
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_select_destroy(self._h)
         self._h = _vp()
 
     def __del__(self):

@@ -86,6 +86,7 @@ typedef struct glu_radix_sort_s* glu_radix_sort;
 typedef struct glu_scan_s* glu_scan;
 typedef struct glu_reduce_s* glu_reduce;
 typedef struct glu_key_runs_s* glu_key_runs;
+typedef struct glu_select_s* glu_select;
 typedef struct glu_timer_s* glu_timer;
 typedef struct glu_dist_s* glu_dist;
 
@@ -560,6 +561,70 @@ GLU_API glu_status glu_key_runs_run_ptr(glu_key_runs runs, const void* keys, siz
  * one can take one tile more), scan_rounds = the rounds the one workgroup that scans the tile counts makes (4096 counts each).
  * Any pointer may be NULL. */
 GLU_API glu_status glu_key_runs_plan(size_t count, uint32_t key_bits, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds);
+
+/* ---- select (not in the reference): stable stream compaction by a stencil and a comparison.  Element i of `count` is SELECTED
+ * iff stencil[i] OP threshold holds; the indices of the selected elements and the items at them are written side by side, in
+ * ascending order of i, and their number is reported.  Keeping the values above a threshold, dropping zeros, keeping the groups
+ * whose batched reduce passed a test: all on the device, on the caller's stream.
+ *   - `stencil` is a device array of one of five element types: the four scalar glu_data_type's FLOAT, DOUBLE, INT, UINT (0 .. 3),
+ *     or GLU_SELECT_STENCIL_BYTE (12), an unsigned byte -- what a bool mask or an array of byte flags is.
+ *   - OP is one of GLU_SELECT_EQ, NE, LT, LE, GT, GE (0 .. 5).
+ *   - `threshold` is a HOST pointer to one value of the stencil's type.  It is read during the call and passed by value to the
+ *     kernels, so that the call stays capturable (a captured call replays with the threshold it was captured with).  NULL means
+ *     zero: the classic "flags" form is UINT or BYTE, GLU_SELECT_NE, NULL.
+ *   - FLOAT and DOUBLE compare as IEEE VALUES: a NaN, in the stencil or as the threshold, satisfies only NE, and -0.0 == +0.0.
+ *     This is deliberately NOT the bit order of the sort (glu_radix_sort_run_typed_ptr puts -0.0 in front of +0.0 and orders the
+ *     NaNs by their payloads) nor the bit equality of key runs: a comparison with a threshold means what it means in C.
+ *     INT compares signed, UINT and BYTE compare unsigned.
+ *   - S = the number of selected elements, i_0 < i_1 < ... their indices: the selection is STABLE.
+ *   - out_indices (uint32, optional, NULL skips it): out_indices[r] = i_r for r < min(S, max_out).
+ *   - out_items (optional; `items` and `out_items` are both NULL or both given): out_items[r] = items[i_r] for
+ *     r < min(S, max_out), copied bit for bit.  item_bytes is 4, 8, 16 or 32 -- the sizes of all twelve glu_data_type's -- and is
+ *     not looked at where items is NULL.  `items` may be the stencil array itself: select-if on the values.
+ *   - *num_selected = S, the true number even where it exceeds max_out: how a caller detects overflow (after synchronising, or
+ *     on the device).
+ *   - THE OVERFLOW RULE: at most max_out entries are written; entries of the two output arrays at or behind min(S, max_out) are
+ *     NOT TOUCHED, and nothing outside the arrays is read or written.  `stencil` and `items` are READ ONLY.
+ *   - count == 0: S = 0, NULL stencil accepted.  With both outputs NULL (or max_out == 0) the call only counts.
+ *   - Limits: count < 2^32; max_out < 2^32; stencil aligned to its element size, items and out_items to min(item_bytes, 16),
+ *     out_indices and num_selected to 4 bytes.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: NULL select; NULL
+ *     stencil with count > 0; NULL num_selected; only one of items and out_items; a stencil_type, op or item_bytes outside the
+ *     lists above; misalignment; the limits above; out_items, out_indices or num_selected overlapping stencil or items (the first
+ *     min(count, max_out) entries of an output array are what can be written; arrays that merely touch are fine).  A refused call
+ *     writes nothing.
+ *   - The call only enqueues on `stream`: no host synchronisation, no side stream, no read-back, and no device allocation once
+ *     glu_select_prepare covered the count (else grow-only allocation inside the call: not capturable).  Three kernels, whose
+ *     grids follow from count and the address of stencil, never from the data: the selected elements of every tile counted
+ *     (glu_select_plan), the counts scanned by one workgroup (the scan of key runs), the selected elements written at their
+ *     ranks.  The stencil is read twice; no workgroup waits for another (no look-back, no atomics, nothing in arrival order), so
+ *     a captured call replays on any contents. */
+#define GLU_SELECT_STENCIL_BYTE 12 /* a stencil of unsigned bytes; the other stencil types are GLU_DATA_TYPE_FLOAT .. _UINT */
+typedef enum glu_select_op
+{
+    GLU_SELECT_EQ = 0,
+    GLU_SELECT_NE,
+    GLU_SELECT_LT,
+    GLU_SELECT_LE,
+    GLU_SELECT_GT,
+    GLU_SELECT_GE,
+    GLU_SELECT_OP_COUNT_
+} glu_select_op;
+GLU_API glu_status glu_select_create(glu_select* out);
+GLU_API glu_status glu_select_destroy(glu_select select);
+/* Grow-only scratch so that the call below allocates nothing (and can be captured) for up to `count` (< 2^32) elements of a
+ * stencil of `stencil_type`: 4 bytes per tile of the stencil. */
+GLU_API glu_status glu_select_prepare(glu_select select, size_t count, int stencil_type);
+/* out_indices[0 .. min(S, max_out)), out_items[0 .. min(S, max_out)) and *num_selected as above; stencil, items and the three
+ * outputs on the DEVICE, threshold on the HOST */
+GLU_API glu_status glu_select_run_ptr(glu_select select, const void* stencil, int stencil_type, int op, const void* threshold,
+                                      size_t count, const void* items, uint32_t item_bytes, void* out_items,
+                                      uint32_t* out_indices, size_t max_out, uint32_t* num_selected, void* stream);
+/* Host only, no device (unit-testable, like glu_key_runs_plan and with its meaning): tile = stencil elements per tile (a whole
+ * number of 16-byte packs), tiles = ceil(count / tile), the tiles of `count` elements that start on a 16-byte boundary (tiles are
+ * counted from the boundary at or below `stencil`: a stencil that starts behind one can take one tile more), scan_rounds = the
+ * rounds the one workgroup that scans the tile counts makes (4096 counts each).  Any pointer may be NULL. */
+GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
