@@ -19,8 +19,14 @@
 //
 // Order of combination: a lane folds its elements in ascending order, groups / waves / workgroups combine in lane, wave and chunk
 // order.  Which element goes to which lane depends on the segment's address (the 16-byte alignment), its length and nothing else:
-// no atomics on values, nothing in arrival order (list positions are, but every item writes a slot of its own and the slots of one
-// segment are adjacent and ordered).  No identity is needed inside the folds (the `has` flags of block_reduce).
+// no atomics on values, nothing in arrival order.  List positions and chunk slots ARE handed out in arrival order (device
+// offsets), and with equal partitions a run of slots starts at partition * chunks; every item writes a slot of its own, the slots
+// of one segment are adjacent and in chunk order, and the one range whose address follows from a slot -- a long segment's run of
+// partials -- is laid out from its own first element, not from a 16-byte boundary (FROM_FIRST below): partials [i * VEC,
+// (i + 1) * VEC) go to lane i mod 256 for every whole pack of VEC = 16 bytes / element size, the fewer than VEC behind the last
+// whole pack one to a lane from lane 0 on, wherever the run lies.  A run on a 16-byte boundary (every call with one long
+// segment) is folded as it was when packs were counted from the boundary.  No identity is needed inside the folds (the `has`
+// flags of block_reduce).
 #pragma once
 
 #include "batch_lists.hpp"
@@ -220,8 +226,12 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_wave_kernel(const Ele
 // ---------------------------------------------------------------------------------------------------------
 // The fold of one contiguous range by a workgroup's threads: elements before the first 16-byte boundary and behind the last whole
 // 16-byte pack go one to a lane, the packs in between are read with 16-byte non-temporal loads, kRbUnroll in flight per lane.
+// FROM_FIRST (the partials of a long segment, whose slot -- and with it the run's alignment -- depends on the order in which
+// segments were binned): the packs are counted from the range's own first element instead, so that which element goes to which
+// lane depends on the range's length alone; a pack is then read 16 bytes at a time only if the range happens to be aligned,
+// element by element otherwise, into the same lane and in the same order.
 // ---------------------------------------------------------------------------------------------------------
-template<int OP, typename S, int N>
+template<int OP, typename S, int N, bool FROM_FIRST = false>
 __device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __restrict__ p, uint32_t len, uint32_t tid, Elem<S, N>& acc, bool& has)
 {
     using T = Elem<S, N>;
@@ -232,20 +242,28 @@ __device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __rest
         has = true;
     };
     uint32_t head = 0;
-    if (VEC > 1)
+    if (VEC > 1 && !FROM_FIRST)
     {
         head = (uint32_t) (((16u - (uint32_t) ((uintptr_t) p & 15u)) & 15u) / sizeof(T));
         if (head > len) head = len;
         if (tid < head) fold(p[tid]);
     }
+    const bool aligned = !FROM_FIRST || ((uintptr_t) p & 15u) == 0; // 16-byte loads are possible (workgroup-uniform)
     const P* packs = reinterpret_cast<const P*>(p + head);
+    auto load_pack = [&](uint32_t i) -> P {
+        if (aligned) return load_streaming(&packs[i]);
+        P v;
+#pragma unroll
+        for (uint32_t k = 0; k < VEC; k++) v.v[k] = p[i * VEC + k]; // (FROM_FIRST: head == 0)
+        return v;
+    };
     const uint32_t npacks = (len - head) / VEC;
     uint32_t i = tid;
     for (; i + (kRbUnroll - 1) * kRbThreads < npacks; i += kRbUnroll * kRbThreads)
     {
         P v[kRbUnroll];
 #pragma unroll
-        for (int u = 0; u < kRbUnroll; u++) v[u] = load_streaming(&packs[i + u * kRbThreads]);
+        for (int u = 0; u < kRbUnroll; u++) v[u] = load_pack(i + u * kRbThreads);
 #pragma unroll
         for (int u = 0; u < kRbUnroll; u++)
 #pragma unroll
@@ -253,7 +271,7 @@ __device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __rest
     }
     for (; i < npacks; i += kRbThreads)
     {
-        const P v = load_streaming(&packs[i]);
+        const P v = load_pack(i);
 #pragma unroll
         for (uint32_t k = 0; k < VEC; k++) fold(v.v[k]);
     }
@@ -267,7 +285,7 @@ __device__ __forceinline__ void reduce_batch_fold_range(const Elem<S, N>* __rest
 // ---------------------------------------------------------------------------------------------------------
 // Medium segments (combine == 0): src = the caller's array, one workgroup per entry of the medium list (or per partition).
 // Long segments' second step (combine == 1): src = the partials, one workgroup per entry of the long list (or per partition) folds
-// the segment's run of partials.
+// the segment's run of partials, laid out from the run's first element.
 // ---------------------------------------------------------------------------------------------------------
 template<int OP, typename S, int N>
 __global__ __launch_bounds__(kRbThreads) void reduce_batch_block_kernel(const Elem<S, N>* __restrict__ src, Elem<S, N>* __restrict__ out,
@@ -304,7 +322,9 @@ __global__ __launch_bounds__(kRbThreads) void reduce_batch_block_kernel(const El
         }
         T acc = zero_elem<S, N>();
         bool has = false;
-        reduce_batch_fold_range<OP>(src + begin, (uint32_t) len, tid, acc, has);
+        // (workgroup-uniform; elements of 16 bytes or more have no packs to count from anywhere)
+        if (sizeof(T) < 16 && combine_partials) reduce_batch_fold_range<OP, S, N, true>(src + begin, (uint32_t) len, tid, acc, has);
+        else reduce_batch_fold_range<OP>(src + begin, (uint32_t) len, tid, acc, has);
         bool rh;
         const T r = block_reduce<OP>(acc, has, wtmp, whas, tid, rh);
         if (tid == 0 && rh) out[seg] = r;

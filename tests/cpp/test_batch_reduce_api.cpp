@@ -1,6 +1,7 @@
 // C++ API test of the batched reduce of glu::Reduce (reduce_batch / reduce_batch_offsets): every segment of an array folded on its
 // own into out[segment], the input left alone -- checked against a plain loop over every slice.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <limits>
 #include <random>
@@ -143,6 +144,47 @@ TEST_CASE("Reduce-batch-offsets-types-and-operators")
     CHECK(run_case<double>(DataType_Double, 1, ReduceOperator_Mul, offsets, total, 0, 5));
     CHECK(run_case<int32_t>(DataType_IVec4, 4, ReduceOperator_Min, offsets, total, 0, 6));
     CHECK(run_case<double>(DataType_DVec4, 4, ReduceOperator_Sum, offsets, total, 0, 7));
+}
+
+/// Four equal partitions that hold the same long float segment of three chunks, every chunk +0.0 but for one element, so that the
+/// three partials are exactly 2^24, 1 and -2^24: (2^24 + 1) - 2^24 is 0 and (2^24 - 2^24) + 1 is 1.  The partitions' runs of
+/// partials start at slots 0, 3, 6 and 9 -- every residue modulo the four floats of a 16-byte pack -- and a result may depend on
+/// the segment's alignment, length and data only: the four must be the same bits.
+TEST_CASE("Reduce-batch-equal-partitions-of-identical-floats-that-round")
+{
+    auto workgroups_of = [](size_t count) {
+        uint32_t path = 0, workgroups = 0;
+        GLU_CHECK_STATUS(glu_reduce_plan_batch(count, (uint32_t) sizeof(float), &path, &workgroups));
+        return path == 3 ? workgroups : 0u;
+    };
+    size_t chunk = 1; // elements of a long segment's chunk (= the longest segment of one workgroup)
+    while (workgroups_of(2 * chunk) == 0) chunk *= 2;
+    const size_t parts = 4, count = 3 * chunk - 8;
+    CHECK(workgroups_of(chunk) == 0);
+    CHECK(workgroups_of(chunk + 1) == 2);
+    CHECK(workgroups_of(count) == 3);
+
+    std::vector<float> data(count * parts, 0.0f);
+    for (size_t p = 0; p < parts; p++)
+    {
+        data[p * count + 12345] = 16777216.0f;
+        data[p * count + chunk + 777] = 1.0f;
+        data[p * count + 2 * chunk + 4321] = -16777216.0f;
+    }
+    std::vector<float> out(parts + 1, 77.0f);
+    ShaderStorageBuffer data_buffer(data);
+    ShaderStorageBuffer out_buffer(out);
+    Reduce reduce(DataType_Float, ReduceOperator_Sum);
+    reduce.reduce_batch(data_buffer.device_ptr(), out_buffer.device_ptr(), count, parts);
+    out = out_buffer.get_data<float>();
+    CHECK(reduce.last_batch().long_segments == parts);
+    for (size_t p = 0; p < parts; p++)
+    {
+        if (std::memcmp(&out[p], &out[0], sizeof(float)) != 0) printf("partition %zu: %g, partition 0: %g\n", p, out[p], out[0]);
+        CHECK(std::memcmp(&out[p], &out[0], sizeof(float)) == 0);
+        CHECK(out[p] == 0.0f || out[p] == 1.0f);
+    }
+    CHECK(out[parts] == 77.0f);
 }
 
 int main(int argc, char** argv) { return mini_test::run(argc, argv); }

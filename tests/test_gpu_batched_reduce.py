@@ -307,6 +307,253 @@ def test_float_sums_that_round(G, dt):
         check(runs[0][:, 0], [d[p * n:(p + 1) * n] for p in range(parts)])
 
 
+def packed_float_types():
+    """The float types with several elements to a 16-byte pack (float, vec2, double): for them the lane an element goes to depends
+    on where the 16-byte boundaries lie."""
+    out = []
+    for dt in range(12):
+        npdt, comps = O.dtype_info(dt)
+        if np.issubdtype(npdt, np.floating) and npdt().itemsize * comps < 16:
+            out.append(dt)
+    return out
+
+
+PACKED_FLOATS = packed_float_types()
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and (a.view(np.uint8) == b.view(np.uint8)).all()
+
+
+def check_rounded(got, d, dt, op, offsets):
+    """Sum: every component of every segment within n * eps * sum|x| of math.fsum (test_float_sums_that_round says why).  Product:
+    within n * eps * |exact product|, the same bound in relative form: each of the n - 1 multiplications is off by a factor of at
+    most 1 + eps / 2 whatever the order, (1 + eps / 2)^(n - 1) - 1 = (n - 1) * eps / 2 * (1 + O(n eps)), and the bound is twice
+    that.  The centre is the product in numpy's longest float, float64 at the least: where that is float64 itself (and the
+    element type is double) the centre can be off by as much as the result, (n - 1) * eps / 2, and the doubled bound still holds
+    both.  Empty segments: the identity, exactly."""
+    npdt, comps = O.dtype_info(dt)
+    eps = float(np.finfo(npdt).eps)
+    rows = d.reshape(-1, comps)
+    for s, (b, e) in enumerate(zip(offsets[:-1], offsets[1:])):
+        n = int(e - b)
+        for c in range(comps):
+            x = rows[b:e, c]
+            value = float(got[s, c])
+            if n == 0:
+                assert value == float(identity(npdt, op)), (s, value)
+            elif op == 0:
+                exact = math.fsum(x.astype(np.float64).tolist())
+                bound = n * eps * math.fsum(np.abs(x).astype(np.float64).tolist())
+                assert abs(value - exact) <= bound, (s, n, value, exact, bound)
+            else:
+                exact = float(np.prod(x.astype(np.longdouble)))
+                bound = n * eps * abs(exact)
+                assert abs(value - exact) <= bound, (s, n, value, exact, bound)
+
+
+@pytest.mark.parametrize("dt", PACKED_FLOATS)
+@pytest.mark.parametrize("op", [0, 1])
+def test_long_float_bits_do_not_depend_on_the_order_of_binning(G, dt, op):
+    """The twin of the batched scan's test of this name.  Three long segments of 3, 5 and 9 chunks among 900 short ones, more than
+    256 segments apart, so that different workgroups of the binning kernel hand out their chunk slots in whatever order they
+    arrive.  A segment's run of partials then starts at a slot that depends on that order -- and whatever the order, at least
+    one run starts at an odd slot (the chunk counts are odd).  Full-mantissa values (Sum: normal; Product: exp(N(0, 0.01)), whose
+    longest product has a logarithm of standard deviation 0.01 * sqrt(9 * 65536) = 7.7, against 87 where float32 ends), so another
+    order of combination shows in the bits.  The whole `out` must be bit for bit the same from call to call, every long
+    segment's result bit for bit what a batch of that segment alone gives on the same array (its partials at slot 0), and every
+    result within the bound of check_rounded."""
+    npdt, comps = O.dtype_info(dt)
+    es = npdt().itemsize * comps
+    wave, block = class_limits(G, es)
+    chunk = block  # (a long segment's chunks are as long as the longest workgroup segment: checked through the plan below)
+    rng = np.random.default_rng(700 + dt * 4 + op)
+    lens = rng.integers(0, 40, 900)
+    long_at = {10: 3, 400: 5, 800: 9}  # segment index: chunks
+    for s, chunks in long_at.items():
+        lens[s] = chunks * chunk - 7
+        assert G.plan_reduce_batch(int(lens[s]), es) == (3, chunks)
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    d = rng.standard_normal(int(offsets[-1]) * comps)
+    if op == 1:
+        d = np.exp(0.01 * d)
+    d = d.astype(npdt)
+    if op == 1:  # far from overflow and underflow: every prefix of the longest segment's product, in float64
+        b, e = int(offsets[800]), int(offsets[801])
+        logs = np.cumsum(np.log(d.reshape(-1, comps)[b:e].astype(np.float64)), axis=0)
+        assert np.abs(logs).max() < 0.5 * math.log(float(np.finfo(np.float32).max)), np.abs(logs).max()
+    red = G.Reduce(dt, op)
+    runs = []
+    for _ in range(3):
+        runs.append(run_offsets(G, red, d, dt, offsets))
+        assert red.read_batch()["long"] == 3
+    assert same_bits(runs[0], runs[1]) and same_bits(runs[0], runs[2]), "the same call gave different bits"
+    for s in long_at:
+        b, e = int(offsets[s]), int(offsets[s + 1])
+        alone = run_offsets(G, red, d, dt, [b, e])
+        assert red.read_batch() == {"wave": 0, "block": 0, "long": 1}
+        print("segment %d (%d chunks): in the batch %r, alone %r" % (s, long_at[s], runs[0][s].tolist(), alone[0].tolist()))
+        assert same_bits(alone[0], runs[0][s]), (s, long_at[s], runs[0][s].tolist(), alone[0].tolist())
+    check_rounded(runs[0], d, dt, op, offsets)
+
+
+def parent_order_of_partials(p, head, vec):
+    """What a workgroup made of a run of at most 16 partials before the partials were laid out from the run's first element:
+    `head` elements in front of the 16-byte boundary one to a lane, then packs of `vec` elements, pack i to lane i, the elements
+    behind the last pack one to a lane again; then the lanes of the wave combined at distances 32, 16, ... 1.  In p's type."""
+    assert len(p) <= 16
+    acc = [None] * 64
+
+    def fold(lane, v):
+        acc[lane] = v if acc[lane] is None else acc[lane] + v
+
+    head = min(head, len(p))
+    for t in range(head):
+        fold(t, p[t])
+    npacks = (len(p) - head) // vec
+    for i in range(npacks):
+        for k in range(vec):
+            fold(i, p[head + i * vec + k])
+    for t in range(head + npacks * vec, len(p)):
+        fold(t - head - npacks * vec, p[t])
+    off = 32
+    while off:
+        new = list(acc)
+        for lane in range(64 - off):
+            if acc[lane + off] is not None:
+                new[lane] = acc[lane + off] if acc[lane] is None else acc[lane] + acc[lane + off]
+        acc, off = new, off // 2
+    return acc[0]
+
+
+# partials whose sum depends on the order of addition, in units of (B, 1) with B = 2 / eps (B + 1 rounds to B): by elements to a
+# 16-byte pack and chunks.  Two elements to a pack and three chunks: both layouts add (p0 + p1) + p2, no set can tell them apart.
+ORDER_SENSITIVE = {
+    (4, 3): "B 1 -B", (4, 5): "B B 1 -B -B", (4, 7): "B B 1 -B 1 1 -B",
+    (2, 3): "B 1 -B", (2, 5): "B B 1 1 -B", (2, 7): "B B B 1 1 -B -B",
+}
+
+
+@pytest.mark.parametrize("dt", PACKED_FLOATS)
+def test_equal_partitions_of_identical_data_give_identical_bits(G, dt):
+    """Four equal partitions that hold the same long segment, of 3, 5 and 7 chunks: their runs of partials start at slots 0, c,
+    2c, 3c, which for an odd c are all residues modulo the elements of a 16-byte pack.  The segment is a multiple of 16 bytes
+    long, so every copy has the same alignment, and the four results must have the same bits -- those of the segment alone
+    through the offsets form.  Two data sets: random normal values, and chunks of +0.0 with one non-zero element each at a random
+    place (so every partial is that element, exactly) chosen so that the order of their addition decides the sum;
+    parent_order_of_partials, on the CPU, shows that they tell the earlier layouts apart."""
+    npdt, comps = O.dtype_info(dt)
+    es = npdt().itemsize * comps
+    vec = 16 // es
+    wave, block = class_limits(G, es)
+    chunk, parts = block, 4
+    rng = np.random.default_rng(800 + dt)
+    red = G.Reduce(dt, 0)
+    big = npdt(2) / np.finfo(npdt).eps
+    for chunks in (3, 5, 7):
+        count = chunks * chunk - 3 * vec
+        assert G.plan_reduce_batch(count, es) == (3, chunks) and count * es % 16 == 0
+        assert sorted((p * chunks) % vec for p in range(parts)) == sorted(p % vec for p in range(parts))
+        partials = [{"B": big, "-B": -big, "1": npdt(1)}[w] for w in ORDER_SENSITIVE[vec, chunks].split()]
+        assert len(partials) == chunks
+        by_head = [parent_order_of_partials(partials, head, vec) for head in range(vec)]
+        print("type %d (%s), %d chunks: the earlier layouts gave %r" % (dt, npdt.__name__, chunks, [float(v) for v in by_head]))
+        assert len(set(float(v) for v in by_head)) >= 2 or (vec == 2 and chunks < 5), "the partials do not tell the layouts apart"
+        engineered = np.zeros((count, comps), dtype=npdt)
+        for c, value in enumerate(partials):
+            at = c * chunk + rng.integers(0, min(chunk, count - c * chunk), comps)
+            engineered[at, np.arange(comps)] = [value, -value][:comps]  # (a second component: the negated set)
+        for name, one in (("normal", rng.standard_normal(count * comps).astype(npdt)), ("engineered", engineered.reshape(-1))):
+            got = run_equal(G, red, np.tile(one, parts), dt, count, parts)
+            assert red.read_batch() == {"wave": 0, "block": 0, "long": parts}
+            alone = run_offsets(G, red, one, dt, [0, count])
+            print("type %d, %d chunks, %s: partitions %r, alone %r" % (dt, chunks, name, got.tolist(), alone[0].tolist()))
+            for p in range(parts):
+                assert same_bits(got[p], got[0]), (chunks, name, p, got.tolist())
+            assert same_bits(got[0], alone[0]), (chunks, name, got[0].tolist(), alone[0].tolist())
+            if name == "engineered":  # (whatever the order, the sum of these is one of a few integers)
+                exact = math.fsum(float(v) for v in partials)
+                assert abs(float(got[0, 0]) - exact) <= chunks and float(got[0, comps - 1]) == (-1) ** (comps - 1) * float(got[0, 0])
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+@pytest.mark.parametrize("shift", [0, 1])
+def test_a_result_depends_on_alignment_length_and_data_only(G, dt, shift):
+    """float and double Sum, one segment length per list (4, 16 and 64 lanes, workgroup, long with two chunks), each a multiple of
+    16 bytes: the same random normal segment five times in one array, filler segments of other multiples of 16 bytes between the
+    copies -- none, a few, more than a binning workgroup holds -- so that the copies have the same address modulo 16 and
+    different segment indices, list positions and neighbours.  The five results have the same bits, and the bits of the five
+    copies laid back to back as equal partitions.  With the array on a 16-byte boundary and one element behind it."""
+    npdt, comps = O.dtype_info(dt)
+    es = npdt().itemsize
+    vec = 16 // es
+    wave, block = class_limits(G, es)
+    two = next(c for c in range(block + 1, 4 * block + 4) if G.plan_reduce_batch(c, es)[1] == 3) - 1  # last length on two workgroups
+    rng = np.random.default_rng(900 + dt * 2 + shift)
+    red = G.Reduce(dt, 0)
+    lists = []
+    for length in (16, 64, wave, block, two):
+        length -= length % vec
+        seg = rng.standard_normal(length).astype(npdt)
+        lens, copies = [], []
+        for fillers in (0, 3, 300, 17, 64):
+            lens += (vec * rng.integers(0, 50, fillers)).tolist()
+            copies.append(len(lens))
+            lens.append(length)
+        lens.append(vec * 5)
+        offsets = np.concatenate([[0], np.cumsum(lens)])
+        d = rng.standard_normal(int(offsets[-1])).astype(npdt)
+        for s in copies:
+            d[offsets[s]:offsets[s + 1]] = seg
+        got = run_offsets(G, red, d, dt, offsets, shift=shift)
+        lists.append(G.plan_reduce_batch(length, es))
+        equal = run_equal(G, red, np.tile(seg, 5), dt, length, 5, shift=shift)
+        print("%s, %d elements, shift %d: %r, as equal partitions %r" % (npdt.__name__, length, shift, got[copies, 0].tolist(), equal[:, 0].tolist()))
+        for s in copies:
+            assert same_bits(got[s], got[copies[0]]), (length, s, got[copies, 0].tolist())
+        for p in range(5):
+            assert same_bits(equal[p], got[copies[0]]), (length, p, equal[:, 0].tolist(), got[copies[0]].tolist())
+        exact = math.fsum(seg.astype(np.float64).tolist())
+        assert abs(float(got[copies[0], 0]) - exact) <= length * float(np.finfo(npdt).eps) * math.fsum(np.abs(seg).astype(np.float64).tolist())
+    assert lists == [(1, 1), (1, 1), (1, 1), (2, 1), (3, 2)] and 16 < 64 < wave  # (up to 16 / up to 64 elements / longer: 4 / 16 / 64 lanes)
+
+
+def test_a_run_of_partials_longer_than_one_round_of_the_workgroup(G):
+    """Two equal partitions of the same 1601 chunks of doubles (random normal, made on the device): 800 packs of two partials and
+    one partial behind them, so the lanes of the workgroup that folds the run take one, three or four packs each, through the
+    loop with four loads in flight and the one behind it.  Partition 0's run lies on a 16-byte boundary and is read with
+    16-byte loads, partition 1's starts at slot 1601 and is read element by element: the same bits, those of the segment alone
+    through the offsets form, within n * eps * sum|x| of the sum torch takes in float64 on the device (pairwise in blocks: its
+    own error is far inside the bound)."""
+    import torch
+
+    dt, chunks = 1, 1601
+    wave, block = class_limits(G, 8)
+    count = chunks * block - 2
+    assert G.plan_reduce_batch(count, 8) == (3, chunks)
+    gen = torch.Generator(device="cuda").manual_seed(17)
+    one = torch.randn(count, generator=gen, device="cuda", dtype=torch.float64)
+    data = torch.cat([one, one])
+    out = torch.full((5,), -1.0, dtype=torch.float64, device="cuda")
+    ot = device_offsets([0, count])
+    red = G.Reduce(dt, 0)
+    red.run_batch_ptr(data.data_ptr(), out.data_ptr(), count, 2, sync_stream())
+    torch.cuda.synchronize()
+    assert red.read_batch() == {"wave": 0, "block": 0, "long": 2}
+    red.run_batch_offsets_ptr(data.data_ptr(), out.data_ptr() + 16, count, ot.data_ptr(), 1, sync_stream())
+    torch.cuda.synchronize()
+    assert red.read_batch() == {"wave": 0, "block": 0, "long": 1}
+    got = out.cpu().numpy()
+    exact, scale = float(one.sum()), float(one.abs().sum())
+    print("partitions %r, alone %r, torch %r" % (got[:2].tolist(), float(got[2]), exact))
+    assert same_bits(got[0:1], got[1:2]) and same_bits(got[0:1], got[2:3]), got[:3].tolist()
+    assert (got[3:] == -1.0).all()
+    assert abs(float(got[0]) - exact) <= count * float(np.finfo(np.float64).eps) * scale
+    del data, one
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("dt,op", [(3, 0), (0, 2)])
 def test_malformed_offsets_read_nothing_outside_the_array(G, dt, op):
     """Offsets that decrease or point beyond `total`: such segments are empty (identity), the well-formed ones are right, and no

@@ -362,6 +362,55 @@ def test_sort_then_by_key(G):
     assert (kt.cpu().numpy().view(np.uint32) == sk).all()
 
 
+def test_by_key_float_sums_that_round(G):
+    """Reduce by key over float32 values whose sums round: sorted uint32 keys with three runs of 3, 5 and 9 chunks of the batched
+    reduce among a few hundred short ones, more than 256 runs apart.  The long runs' chunk slots are handed out in arrival
+    order, and with odd chunk counts at least one run of partials starts at an odd slot.  Two calls give the same bits, and
+    every long run's sum has the bits of the batched reduce of that slice alone, on the same array."""
+    import torch
+
+    chunk = 1  # float32 elements of the longest workgroup segment = of a chunk of a long one
+    while G.plan_reduce_batch(2 * chunk, 4)[0] < 3:
+        chunk *= 2
+    assert G.plan_reduce_batch(chunk, 4) == (2, 1) and G.plan_reduce_batch(chunk + 1, 4) == (3, 2)
+    rng = np.random.default_rng(71)
+    lens = rng.integers(1, 40, 700)
+    long_at = {5: 3, 330: 5, 650: 9}  # run: chunks
+    for r, chunks in long_at.items():
+        lens[r] = chunks * chunk - 7
+        assert G.plan_reduce_batch(int(lens[r]), 4) == (3, chunks)
+    heads = np.concatenate([[0], np.cumsum(lens)])
+    n, R = int(heads[-1]), lens.size
+    max_runs = R + 9
+    keys = np.repeat(np.cumsum(rng.integers(1, 1000, R)).astype(np.uint32), lens)
+    vals = rng.standard_normal(n).astype(np.float32)
+    ka, va = Array(keys), Array(vals)
+    runs, red = G.KeyRuns(), G.Reduce(G.DataType_Float, G.ReduceOperator_Sum)
+    results = []
+    for _ in range(2):
+        oa, na, out = Array.poisoned(max_runs + 1, np.uint32), Array.poisoned(1, np.uint32), Array.poisoned(max_runs, np.float32)
+        red.run_by_key_ptr(runs, ka.ptr, va.ptr, out.ptr, n, oa.ptr, max_runs, na.ptr, stream=stream())
+        torch.cuda.synchronize()
+        assert int(na.result()[0]) == R and (oa.result() == expected(keys, 0xFFFFFFFF, max_runs)[0]).all()
+        assert red.read_batch()["long"] == 3
+        results.append(out.result())
+    assert (va.result().view(np.uint32) == vals.view(np.uint32)).all() and (ka.result() == keys).all()
+    assert (results[0].view(np.uint8) == results[1].view(np.uint8)).all(), "the same call gave different bits"
+    got = results[0]
+    assert (got[R:] == 0).all()
+    sums = np.add.reduceat(vals.astype(np.float64), heads[:-1])
+    scale = np.add.reduceat(np.abs(vals).astype(np.float64), heads[:-1])
+    assert (np.abs(got[:R] - sums) <= lens * float(np.finfo(np.float32).eps) * scale).all()  # (n * eps * sum|x|, as in the batched reduce's tests)
+    for r, chunks in long_at.items():
+        one, alone = Array(np.asarray([heads[r], heads[r + 1]], dtype=np.uint32)), Array.poisoned(1, np.float32)
+        red.run_batch_offsets_ptr(va.ptr, alone.ptr, n, one.ptr, 1, stream())
+        torch.cuda.synchronize()
+        assert red.read_batch() == {"wave": 0, "block": 0, "long": 1}
+        a, b = alone.result(), got[r:r + 1]
+        print("run %d (%d chunks): by key %r, alone %r" % (r, chunks, float(b[0]), float(a[0])))
+        assert (a.view(np.uint8) == b.view(np.uint8)).all(), (r, chunks, float(b[0]), float(a[0]))
+
+
 def test_argument_checks(G):
     import torch
 
