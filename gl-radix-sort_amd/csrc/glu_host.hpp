@@ -13,6 +13,7 @@
 //   glu_key_runs.hip          key runs: the offsets of the runs of equal keys, for the three batched units (key_runs_kernels.hpp)
 //   glu_select.hip            select: stable stream compaction by a stencil and a comparison (select_kernels.hpp)
 // The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
+// Key runs and select share glu_tile_host.hpp on the host side and tile_span.hpp (the tiles) on both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,42 +1,25 @@
 // glu_key_runs.hip -- key runs of libglu_hip.so (key_runs_kernels.hpp): glu_key_runs_create, glu_key_runs_destroy,
-// glu_key_runs_prepare, glu_key_runs_run_ptr, glu_key_runs_plan.
+// glu_key_runs_prepare, glu_key_runs_run_ptr, glu_key_runs_plan; and the launch of the count scan that key runs and select share
+// (glu_tile_host.hpp).
 // The library's other translation units: glu_host.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "glu_batch_host.hpp"
 #include "glu_key_runs_object.hpp"
 #include "key_runs_kernels.hpp"
+#include "tile_count_scan_kernel.hpp"
 
 using namespace glu_hip;
 using namespace glu_hip::host;
 
 namespace
 {
-glu_status check_count(size_t count)
-{
-    return count < ((size_t) 1 << 32) ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "key runs take fewer than 2^32 keys (got %zu)", count);
-}
+glu_status check_count(size_t count) { return check_tile_count(count, "key runs take fewer than 2^32 keys"); }
 
 glu_status check_key_bits(uint32_t key_bits)
 {
     return key_bits == 32 || key_bits == 64 ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "key_bits must be 32 or 64 (got %u)", key_bits);
-}
-
-// The tile counts of `count` keys.  A base that is not 16-byte aligned moves the keys up to a pack's length into the first tile,
-// which can add a tile behind the last: one more than the plan's.
-glu_status reserve_tiles(glu_key_runs_s* r, size_t count, uint32_t key_bits)
-{
-    uint32_t tile, tiles, rounds;
-    key_runs_plan(count, key_bits / 8, tile, tiles, rounds);
-    return count ? r->tile_counts.reserve(((size_t) tiles + 1) * sizeof(uint32_t)) : GLU_OK;
-}
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 struct Call
@@ -58,24 +41,19 @@ struct Call
 template<typename K>
 glu_status run(const Call& c)
 {
-    using C = KeyRunsCfg<K>;
     KeyRunsArgs<K> a;
-    a.lo = ((uintptr_t) c.keys & 15u) / sizeof(K);
-    a.hi = a.lo + c.count;
-    a.base = (const K*) c.keys - a.lo;
+    a.keys = tile_span<K, kKeyRunsPacks>(c.keys, c.count);
     const uint32_t width = c.end_bit - c.begin_bit;
     a.mask = width == 0 ? (K) 0 : (K) ((width >= 8 * sizeof(K) ? ~(K) 0 : (((K) 1 << width) - 1)) << c.begin_bit);
-    a.tiles = c.count ? (uint32_t) ((a.hi + C::TILE - 1) / C::TILE) : 0u;
+    const uint32_t tiles = a.keys.tiles;
     uint32_t* tile_counts = (uint32_t*) c.runs->tile_counts.ptr;
-    const uint32_t device_grid = cus() * 8u;
-    hipLaunchKernelGGL((key_runs_count_kernel<K>), dim3(std::max(1u, std::min(a.tiles, device_grid))), dim3(kKrThreads), 0, c.stream, a,
-                       tile_counts);
+    hipLaunchKernelGGL((key_runs_count_kernel<K>), dim3(tile_grid(tiles)), dim3(kTileThreads), 0, c.stream, a, tile_counts);
     HIP_TRY(hipGetLastError());
-    GLU_TRY(launch_tile_count_scan(tile_counts, a.tiles, c.num_runs, c.stream));
+    GLU_TRY(launch_tile_count_scan(tile_counts, tiles, c.num_runs, c.stream));
     // (the fill: a workgroup per 4096 entries of offsets, if the tiles ask for fewer)
-    const uint32_t fill_blocks = (uint32_t) std::min<uint64_t>((c.max_runs + 1 + 4095) / 4096, device_grid);
-    hipLaunchKernelGGL((key_runs_write_kernel<K>), dim3(std::max(fill_blocks, std::min(a.tiles, device_grid))), dim3(kKrThreads), 0, c.stream,
-                       a, (const uint32_t*) tile_counts, (const uint32_t*) c.num_runs, (K*) c.unique_keys, c.offsets, (uint32_t) c.max_runs);
+    const uint32_t fill_blocks = tile_grid((uint32_t) ((c.max_runs + 1 + 4095) / 4096));
+    hipLaunchKernelGGL((key_runs_write_kernel<K>), dim3(std::max(fill_blocks, tile_grid(tiles))), dim3(kTileThreads), 0, c.stream, a,
+                       (const uint32_t*) tile_counts, (const uint32_t*) c.num_runs, (K*) c.unique_keys, c.offsets, (uint32_t) c.max_runs);
     HIP_TRY(hipGetLastError());
     return GLU_OK;
 }
@@ -88,19 +66,16 @@ glu_status glu_hip::host::launch_tile_count_scan(uint32_t* tile_counts, uint32_t
     return GLU_OK;
 }
 
-uint32_t glu_hip::host::tile_count_scan_rounds(uint32_t tiles) { return (tiles + kKrScanRound - 1) / kKrScanRound; }
-
 extern "C" {
 
 glu_status glu_key_runs_plan(size_t count, uint32_t key_bits, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds)
 {
     GLU_TRY(check_key_bits(key_bits));
     GLU_TRY(check_count(count));
-    uint32_t t, n, r;
-    key_runs_plan(count, key_bits / 8, t, n, r);
-    if (tile) *tile = t;
-    if (tiles) *tiles = n;
-    if (scan_rounds) *scan_rounds = r;
+    const TilePlan p = tile_plan(count, key_bits / 8, kKeyRunsPacks);
+    if (tile) *tile = p.tile;
+    if (tiles) *tiles = p.tiles;
+    if (scan_rounds) *scan_rounds = p.scan_rounds;
     return GLU_OK;
 }
 
@@ -128,7 +103,7 @@ glu_status glu_key_runs_prepare(glu_key_runs runs, size_t count, uint32_t key_bi
     if (!runs) return fail(GLU_ERROR_INVALID_ARGUMENT, "runs is NULL");
     GLU_TRY(check_key_bits(key_bits));
     GLU_TRY(check_count(count));
-    return reserve_tiles(runs, count, key_bits);
+    return runs->tile_counts.reserve(count, key_bits / 8, kKeyRunsPacks);
 }
 
 glu_status glu_key_runs_run_ptr(glu_key_runs runs, const void* keys, size_t count, uint32_t key_bits, uint32_t begin_bit,
@@ -154,7 +129,7 @@ glu_status glu_key_runs_run_ptr(glu_key_runs runs, const void* keys, size_t coun
     if (unique_keys && overlaps(keys, count * key_bytes, unique_keys, max_runs * key_bytes))
         return fail(GLU_ERROR_INVALID_ARGUMENT, "unique_keys overlaps keys");
     if (overlaps(keys, count * key_bytes, num_runs, sizeof(uint32_t))) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_runs overlaps keys");
-    GLU_TRY(reserve_tiles(runs, count, key_bits));
+    GLU_TRY(runs->tile_counts.reserve(count, key_bits / 8, kKeyRunsPacks));
     const Call c{runs, keys, count, begin_bit, end_bit, unique_keys, offsets, max_runs, num_runs, pick_stream(stream)};
     return key_bits == 64 ? run<uint64_t>(c) : run<uint32_t>(c);
 }

@@ -6,8 +6,6 @@
 #include <algorithm>
 #include <cstring>
 
-#include "glu_batch_host.hpp"
-#include "glu_key_runs_object.hpp"
 #include "glu_select_object.hpp"
 #include "select_kernels.hpp"
 
@@ -20,10 +18,7 @@ static_assert(GLU_SELECT_EQ == SELECT_EQ && GLU_SELECT_NE == SELECT_NE && GLU_SE
 
 namespace
 {
-glu_status check_count(size_t count)
-{
-    return count < ((size_t) 1 << 32) ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "select takes a count below 2^32 (got %zu)", count);
-}
+glu_status check_count(size_t count) { return check_tile_count(count, "select takes a count below 2^32"); }
 
 // bytes of a stencil element, 0 for what is no stencil type
 uint32_t stencil_bytes(int stencil_type)
@@ -47,21 +42,6 @@ glu_status check_stencil_type(int stencil_type)
                       stencil_type);
 }
 
-// The tile counts of `count` elements.  A base that is not 16-byte aligned moves the elements up to a pack's length into the first
-// tile, which can add a tile behind the last: one more than the plan's.
-glu_status reserve_tiles(glu_select_s* s, size_t count, int stencil_type)
-{
-    uint32_t tile, tiles;
-    select_plan(count, stencil_bytes(stencil_type), tile, tiles);
-    return count ? s->tile_counts.reserve(((size_t) tiles + 1) * sizeof(uint32_t)) : GLU_OK;
-}
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 struct Call
 {
     glu_select_s* sel;
@@ -81,7 +61,7 @@ struct Call
 template<typename S, uint32_t ITEM_BYTES>
 void launch_write(const Call& c, const SelectArgs<S>& a, const uint32_t* tile_counts, uint32_t grid)
 {
-    hipLaunchKernelGGL((select_write_kernel<S, ITEM_BYTES>), dim3(grid), dim3(kSelThreads), 0, c.stream, a, tile_counts, c.items, c.out_items,
+    hipLaunchKernelGGL((select_write_kernel<S, ITEM_BYTES>), dim3(grid), dim3(kTileThreads), 0, c.stream, a, tile_counts, c.items, c.out_items,
                        c.out_indices, (uint32_t) c.max_out);
 }
 
@@ -91,21 +71,17 @@ void launch_write(const Call& c, const SelectArgs<S>& a, const uint32_t* tile_co
 template<typename S>
 glu_status run(const Call& c)
 {
-    using C = SelectCfg<S>;
     SelectArgs<S> a;
-    a.lo = ((uintptr_t) c.stencil & 15u) / sizeof(S);
-    a.hi = a.lo + c.count;
-    a.base = (const S*) c.stencil - a.lo;
+    a.stencil = tile_span<S, SelectCfg<S>::PACKS>(c.stencil, c.count);
     S threshold = (S) 0; // (NULL: zero)
     if (c.threshold) memcpy(&threshold, c.threshold, sizeof(S));
     a.pred = make_select_pred<S>(c.op, threshold);
-    a.tiles = c.count ? (uint32_t) ((a.hi + C::TILE - 1) / C::TILE) : 0u;
+    const uint32_t tiles = a.stencil.tiles, grid = tile_grid(tiles);
     uint32_t* tile_counts = (uint32_t*) c.sel->tile_counts.ptr;
-    const uint32_t grid = std::max(1u, std::min(a.tiles, cus() * 8u));
-    hipLaunchKernelGGL((select_count_kernel<S>), dim3(grid), dim3(kSelThreads), 0, c.stream, a, tile_counts);
+    hipLaunchKernelGGL((select_count_kernel<S>), dim3(grid), dim3(kTileThreads), 0, c.stream, a, tile_counts);
     HIP_TRY(hipGetLastError());
-    GLU_TRY(launch_tile_count_scan(tile_counts, a.tiles, c.num_selected, c.stream));
-    if (!a.tiles || !c.max_out || (!c.out_items && !c.out_indices)) return GLU_OK; // (nothing can be written: the call only counts)
+    GLU_TRY(launch_tile_count_scan(tile_counts, tiles, c.num_selected, c.stream));
+    if (!tiles || !c.max_out || (!c.out_items && !c.out_indices)) return GLU_OK; // (nothing can be written: the call only counts)
     switch (c.items ? c.item_bytes : 0u)
     {
     case 0: launch_write<S, 0>(c, a, tile_counts, grid); break;
@@ -125,11 +101,11 @@ glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint3
 {
     GLU_TRY(check_stencil_type(stencil_type));
     GLU_TRY(check_count(count));
-    uint32_t t, n;
-    select_plan(count, stencil_bytes(stencil_type), t, n);
-    if (tile) *tile = t;
-    if (tiles) *tiles = n;
-    if (scan_rounds) *scan_rounds = tile_count_scan_rounds(n);
+    const uint32_t sb = stencil_bytes(stencil_type);
+    const TilePlan p = tile_plan(count, sb, select_packs(sb));
+    if (tile) *tile = p.tile;
+    if (tiles) *tiles = p.tiles;
+    if (scan_rounds) *scan_rounds = p.scan_rounds;
     return GLU_OK;
 }
 
@@ -157,7 +133,8 @@ glu_status glu_select_prepare(glu_select select, size_t count, int stencil_type)
     if (!select) return fail(GLU_ERROR_INVALID_ARGUMENT, "select is NULL");
     GLU_TRY(check_stencil_type(stencil_type));
     GLU_TRY(check_count(count));
-    return reserve_tiles(select, count, stencil_type);
+    const uint32_t sb = stencil_bytes(stencil_type);
+    return select->tile_counts.reserve(count, sb, select_packs(sb));
 }
 
 glu_status glu_select_run_ptr(glu_select select, const void* stencil, int stencil_type, int op, const void* threshold, size_t count,
@@ -196,7 +173,7 @@ glu_status glu_select_run_ptr(glu_select select, const void* stencil, int stenci
         for (const auto& i : inputs)
             if (o.ptr && i.ptr && overlaps(i.ptr, i.bytes, o.ptr, o.bytes))
                 return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", o.name, i.name);
-    GLU_TRY(reserve_tiles(select, count, stencil_type));
+    GLU_TRY(select->tile_counts.reserve(count, (uint32_t) sb, select_packs((uint32_t) sb)));
     const Call c{select, stencil, op, threshold, count, items, item_bytes, out_items, out_indices, max_out, num_selected, pick_stream(stream)};
     switch (stencil_type)
     {

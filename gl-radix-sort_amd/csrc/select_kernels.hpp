@@ -2,34 +2,22 @@
 // stencil[i] OP threshold holds; the indices of the selected elements, and the items at them, are written in ascending order of i.
 // Not in the reference.
 //
-// The shape of key runs (key_runs_kernels.hpp) with another flag function.  Three kernels, whatever the stencil holds:
-//   select_count_kernel   tile_counts[t] = selected elements of tile t.  A tile is SelectCfg::TILE elements: 256 threads x GROUPS
-//                         packs of 16 bytes (four packs of 4- and 8-byte stencils, one pack of 16 byte stencils), wave-major, then
-//                         pack, then lane, then the elements of a pack, so that the order of (wave, pack, lane, element) is the
-//                         order of the elements.  Tiles are counted from the 16-byte boundary at or below `stencil`: every pack is
-//                         aligned, whole packs take one 16-byte load, the packs that hold the first and the last element go
-//                         element by element, and nothing outside the array is read.  One ballot + popcount per element position
-//                         of a pack, the four wave sums through LDS, one barrier per tile (two rows of LDS in turn).
-//   key_runs_scan_kernel  (key_runs_kernels.hpp, launched through host::launch_tile_count_scan) the counts scanned exclusively in
-//                         place by one workgroup, the total written to *num_selected.
-//   select_write_kernel   the flags of a tile again; the rank of a selected element = tile_counts[t] + the wave sums below its wave
-//                         (LDS) + the selected elements below it in its wave (mbcnt of the ballots); out_indices[rank] = i and
-//                         out_items[rank] = items[i] where rank < max_out.  An item is loaded where its flag is set and its rank is
-//                         in range, and stored at once: no lane holds more than one item (two 16-byte words at most).
-// OP is a run-time, workgroup-uniform argument, folded on the host into a SelectPred.  The stencil is read twice; nothing waits for
-// another workgroup: no look-back, no atomics, no arrival order.  Both streaming kernels run a grid sized to the device and walk
-// the tiles in a loop.
+// Select is a flag-and-compact operator (tile_compact_kernels.hpp: the tiles, the load of a pack, the count per tile, the ranks);
+// what it adds:
+//   the flags   select_flags: a predicate on the element.  OP is a run-time, workgroup-uniform argument, folded on the host into a
+//               SelectPred, and evaluated only on elements of the array: a zero read as padding would pass EQ 0.
+//   the tile    four packs of 4- and 8-byte stencils per thread, one pack of 16 byte stencils.
+//   the write   out_indices[rank] = i and out_items[rank] = items[i] where rank < max_out.  An item is loaded where its flag is set
+//               and its rank is in range, and stored at once: no lane holds more than one item (two 16-byte words at most).
+// The stencil is read twice.
 #pragma once
 
 #include <type_traits>
 
-#include "scan_batch_kernels.hpp"
+#include "tile_compact_kernels.hpp"
 
 namespace glu_hip
 {
-constexpr int kSelThreads = kSbThreads;
-constexpr int kSelWaves = kSelThreads / kW;
-
 enum
 {
     SELECT_EQ = 0,
@@ -41,15 +29,10 @@ enum
     SELECT_OPS_
 };
 
+// packs per thread and tile
+constexpr uint32_t select_packs(uint32_t stencil_bytes) { return stencil_bytes == 1 ? 1u : 4u; }
 template<typename S>
-struct SelectCfg
-{
-    static constexpr uint32_t VEC = 16 / (uint32_t) sizeof(S);
-    static constexpr uint32_t GROUPS = sizeof(S) == 1 ? 1 : 4; // packs per thread and tile
-    static constexpr uint32_t WAVE_ELEMS = kW * GROUPS * VEC;
-    static constexpr uint32_t TILE = kSelWaves * WAVE_ELEMS;
-    static_assert(GROUPS * VEC <= 32, "a lane's flags are the bits of one word");
-};
+using SelectCfg = TileCfg<sizeof(S), select_packs(sizeof(S))>;
 
 // The comparison of one call, folded on the host (make_select_pred).
 // Integers (int32_t, uint32_t, uint8_t): every one of the six comparisons with a constant is "x lies in [a, b]" or its negation,
@@ -125,79 +108,34 @@ inline SelectPred<S> make_select_pred(int op, S threshold)
     return p;
 }
 
-// host only: elements per tile, tiles of `count` elements from an aligned base (the rounds of the count scan:
-// host::tile_count_scan_rounds)
-inline void select_plan(uint64_t count, uint32_t stencil_bytes, uint32_t& tile, uint32_t& tiles)
-{
-    tile = stencil_bytes == 8 ? SelectCfg<uint64_t>::TILE : stencil_bytes == 1 ? SelectCfg<uint8_t>::TILE : SelectCfg<uint32_t>::TILE;
-    tiles = (uint32_t) ((count + tile - 1) / tile);
-}
-
-// What a call passes to its two streaming kernels.  `base` is the 16-byte boundary at or below the stencil; the stencil is the
-// elements [lo, hi) of it (lo < VEC).
+// What a call passes to its two streaming kernels.
 template<typename S>
 struct SelectArgs
 {
-    const S* base;
-    uint64_t lo, hi;
+    TileSpan<S> stencil;
     SelectPred<S> pred;
-    uint32_t tiles;
 };
 
-// The flags of the calling lane's elements of tile `t`: bit g * VEC + k for element k of the lane's pack g.  Elements outside
-// [lo, hi) are not read and not selected.  first = the lane's pack 0 as an element of `base`; pack g: + g * kW * VEC.
+// The flags of the calling lane's elements of a tile (`first`: its pack 0).  Elements outside the array are not selected.
 template<typename S>
-__device__ __forceinline__ uint32_t select_flags(const SelectArgs<S>& a, uint32_t t, uint32_t wave, uint32_t lane, uint64_t& first)
+__device__ __forceinline__ uint32_t select_flags(const SelectArgs<S>& a, uint64_t first)
 {
     using C = SelectCfg<S>;
-    first = (uint64_t) t * C::TILE + wave * C::WAVE_ELEMS + lane * C::VEC;
     uint32_t flags = 0;
 #pragma unroll
-    for (uint32_t g = 0; g < C::GROUPS; g++)
-    {
-        const uint64_t v0 = first + g * kW * C::VEC;
-        if (v0 >= a.lo && v0 + C::VEC <= a.hi)
-        {
-            const Pack<S, C::VEC> pk = *reinterpret_cast<const Pack<S, C::VEC>*>(a.base + v0);
-#pragma unroll
-            for (uint32_t k = 0; k < C::VEC; k++) flags |= (a.pred(pk.v[k]) ? 1u : 0u) << (g * C::VEC + k);
-        }
-        else
-        {
-#pragma unroll
-            for (uint32_t k = 0; k < C::VEC; k++)
-                if (v0 + k >= a.lo && v0 + k < a.hi) flags |= (a.pred(a.base[v0 + k]) ? 1u : 0u) << (g * C::VEC + k);
-        }
-    }
+    for (uint32_t g = 0; g < C::PACKS; g++)
+        tile_load_pack<C::VEC>(a.stencil, first + g * C::PACK_STRIDE, [&](uint32_t k, S x, bool inside) {
+            if (inside) flags |= (a.pred(x) ? 1u : 0u) << (g * C::VEC + k);
+        });
     return flags;
 }
 
 template<typename S>
-__global__ __launch_bounds__(kSelThreads) void select_count_kernel(SelectArgs<S> a, uint32_t* __restrict__ tile_counts)
+__global__ __launch_bounds__(kTileThreads) void select_count_kernel(SelectArgs<S> a, uint32_t* __restrict__ tile_counts)
 {
-    using C = SelectCfg<S>;
-    __shared__ uint32_t wsum[2][kSelWaves];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t phase = 0;
-    for (uint32_t t = blockIdx.x; t < a.tiles; t += gridDim.x) // (workgroup-uniform)
-    {
-        uint64_t first;
-        const uint32_t flags = select_flags(a, t, wave, lane, first);
-        uint32_t n = 0;
-#pragma unroll
-        for (uint32_t b = 0; b < C::GROUPS * C::VEC; b++) n += (uint32_t) __popcll(__ballot((flags >> b) & 1u));
-        uint32_t* row = wsum[phase & 1u];
-        phase++;
-        if (lane == 0) row[wave] = n;
-        __syncthreads();
-        if (threadIdx.x == 0)
-        {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int w = 0; w < kSelWaves; w++) sum += row[w];
-            tile_counts[t] = sum;
-        }
-    }
+    TileWalk<SelectCfg<S>> w;
+    for (uint32_t t = blockIdx.x; t < a.stencil.tiles; t += gridDim.x) // (workgroup-uniform)
+        tile_count(w, t, select_flags(a, w.first(t)), tile_counts);
 }
 
 // An item of ITEM_BYTES (4, 8, 16 or 32) bytes, copied bit for bit; 16 and 32 bytes move as 16-byte words.
@@ -219,71 +157,27 @@ struct SelectItem<8>
 
 // ITEM_BYTES == 0: no items (indices only).  out_indices may be NULL where ITEM_BYTES != 0.
 template<typename S, uint32_t ITEM_BYTES>
-__global__ __launch_bounds__(kSelThreads) void select_write_kernel(SelectArgs<S> a, const uint32_t* __restrict__ tile_counts,
-                                                                   const void* __restrict__ items, void* __restrict__ out_items,
-                                                                   uint32_t* __restrict__ out_indices, uint32_t max_out)
+__global__ __launch_bounds__(kTileThreads) void select_write_kernel(SelectArgs<S> a, const uint32_t* __restrict__ tile_counts,
+                                                                    const void* __restrict__ items, void* __restrict__ out_items,
+                                                                    uint32_t* __restrict__ out_indices, uint32_t max_out)
 {
-    using C = SelectCfg<S>;
     using Word = typename SelectItem<ITEM_BYTES>::Word;
     constexpr uint32_t WORDS = ITEM_BYTES ? ITEM_BYTES / (uint32_t) sizeof(Word) : 0u;
-    __shared__ uint32_t wsum[2][kSelWaves];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t phase = 0;
-    for (uint32_t t = blockIdx.x; t < a.tiles; t += gridDim.x) // (workgroup-uniform)
-    {
-        uint64_t first;
-        const uint32_t flags = select_flags(a, t, wave, lane, first);
-        uint32_t below[C::GROUPS]; // selected elements of the wave in front of the lane's pack g
-        uint32_t wave_total = 0;
-#pragma unroll
-        for (uint32_t g = 0; g < C::GROUPS; g++)
-        {
-            uint32_t mine = 0, all = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < C::VEC; k++)
+    TileWalk<SelectCfg<S>> w;
+    for (uint32_t t = blockIdx.x; t < a.stencil.tiles; t += gridDim.x) // (workgroup-uniform)
+        tile_compact(w, t, select_flags(a, w.first(t)), a.stencil, tile_counts, [&](uint32_t rank, uint32_t, uint32_t, uint32_t i) {
+            if (rank < max_out)
             {
-                const uint64_t b = __ballot((flags >> (g * C::VEC + k)) & 1u);
-                mine += __builtin_amdgcn_mbcnt_hi((uint32_t) (b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) b, 0u));
-                all += (uint32_t) __popcll(b);
-            }
-            below[g] = wave_total + mine;
-            wave_total += all;
-        }
-        uint32_t* row = wsum[phase & 1u];
-        phase++;
-        if (lane == 0) row[wave] = wave_total;
-        __syncthreads();
-        uint32_t base = tile_counts[t];
-#pragma unroll
-        for (int w = 0; w < kSelWaves; w++)
-            if ((uint32_t) w < wave) base += row[w];
-#pragma unroll
-        for (uint32_t g = 0; g < C::GROUPS; g++)
-        {
-            // (mbcnt counted the lanes below for every element position: the lane's own earlier elements of the pack are added here)
-            uint32_t rank = base + below[g];
-#pragma unroll
-            for (uint32_t k = 0; k < C::VEC; k++)
-            {
-                if ((flags >> (g * C::VEC + k)) & 1u)
+                if (out_indices) out_indices[rank] = i;
+                if constexpr (ITEM_BYTES != 0)
                 {
-                    if (rank < max_out)
-                    {
-                        const uint32_t i = (uint32_t) (first + g * kW * C::VEC + k - a.lo);
-                        if (out_indices) out_indices[rank] = i;
-                        if constexpr (ITEM_BYTES != 0)
-                        {
-                            const Word* src = reinterpret_cast<const Word*>(items) + (uint64_t) i * WORDS;
-                            Word* dst = reinterpret_cast<Word*>(out_items) + (uint64_t) rank * WORDS;
+                    const Word* src = reinterpret_cast<const Word*>(items) + (uint64_t) i * WORDS;
+                    Word* dst = reinterpret_cast<Word*>(out_items) + (uint64_t) rank * WORDS;
 #pragma unroll
-                            for (uint32_t w = 0; w < WORDS; w++) dst[w] = src[w];
-                        }
-                    }
-                    rank++;
+                    for (uint32_t n = 0; n < WORDS; n++) dst[n] = src[n];
                 }
             }
-        }
-    }
+        });
 }
 
 } // namespace glu_hip
