@@ -20,6 +20,9 @@ ReduceOperator_Sum, ReduceOperator_Mul, ReduceOperator_Min, ReduceOperator_Max =
 # glu_select_run_ptr: the stencil types (the four scalar data types with their values, and a byte) and the comparisons
 SelectStencil_Float, SelectStencil_Double, SelectStencil_Int, SelectStencil_Uint, SelectStencil_Byte = 0, 1, 2, 3, 12
 SelectOperator_EQ, SelectOperator_NE, SelectOperator_LT, SelectOperator_LE, SelectOperator_GT, SelectOperator_GE = range(6)
+# glu_sorted_search_set_option("PATH", ...) and what glu_sorted_search_plan / glu_sorted_search_last report
+SearchPath_Auto, SearchPath_Direct, SearchPath_Indexed = range(3)
+KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2, "uint64": 3, "int64": 4, "float64": 5}  # glu_key_type by numpy dtype name
 
 GLU_OK = 0
 GLU_ERROR_INVALID_ARGUMENT = 1
@@ -113,6 +116,14 @@ SYMBOLS = [
     ("glu_select_prepare", _int, [_vp, _sz, _int]),
     ("glu_select_run_ptr", _int, [_vp, _vp, _int, _int, _vp, _sz, _vp, _u32, _vp, _vp, _sz, _vp, _vp]),
     ("glu_select_plan", _int, [_sz, _int, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_sorted_search_create", _int, [_P(_vp)]),
+    ("glu_sorted_search_destroy", _int, [_vp]),
+    ("glu_sorted_search_prepare", _int, [_vp, _sz, _int]),
+    ("glu_sorted_search_set_option", _int, [_vp, ctypes.c_char_p, ctypes.c_longlong]),
+    ("glu_sorted_search_index_ptr", _int, [_vp, _vp, _sz, _int, _vp]),
+    ("glu_sorted_search_run_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _int, _vp]),
+    ("glu_sorted_search_plan", _int, [_sz, _sz, _int, _u32, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_sorted_search_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -313,6 +324,16 @@ def plan_select(count, stencil_type=SelectStencil_Uint):
     a, b, c = _u32(0), _u32(0), _u32(0)
     check(lib().glu_select_plan(count, stencil_type, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
     return a.value, b.value, c.value
+
+
+def plan_sorted_search(hay_count, needle_count, key_type="uint32", top_entries=0):
+    """(path, levels, fanout, index_bytes) of a sorted search of `needle_count` needles in `hay_count` keys on the AUTO path
+    (glu_sorted_search_plan; host only): SearchPath_Direct or SearchPath_Indexed, the levels L of the index (whatever the path), the
+    keys to a 128-byte line, the bytes of the index.  top_entries 0: the default, what LDS holds."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_sorted_search_plan(hay_count, needle_count, KEY_TYPES[key_type], top_entries, ctypes.byref(a), ctypes.byref(b),
+                                       ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
 
 
 def _read_batch(fn, handle):
@@ -561,6 +582,60 @@ class Select:
     def destroy(self):
         if self._h and _lib is not None:
             _lib.glu_select_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class SortedSearch:
+    """glu::SortedSearch (not in the reference) over the C ABI: lower and upper bounds of many needles in a sorted haystack."""
+
+    NEEDLE_PACKS = 2  # 16-byte packs of needles per thread and tile (sorted_search_kernels.hpp: kSearchPacks)
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_sorted_search_create(ctypes.byref(self._h)))
+
+    @classmethod
+    def needle_tile(cls, key_type="uint32"):
+        """Needles per tile of the indexed search kernel: 256 threads x NEEDLE_PACKS packs of 16 bytes."""
+        return 256 * cls.NEEDLE_PACKS * (16 // np.dtype(key_type).itemsize)
+
+    def prepare(self, hay_count, key_type="uint32"):
+        """Scratch for the index of `hay_count` keys at the TOP_ENTRIES set now: later calls allocate nothing (capturable)
+        (glu_sorted_search_prepare)."""
+        check(lib().glu_sorted_search_prepare(self._h, hay_count, KEY_TYPES[key_type]))
+
+    def set_option(self, name, value):
+        """"PATH": SearchPath_Auto, _Direct or _Indexed; "TOP_ENTRIES": the most entries of the index's top level
+        (glu_sorted_search_set_option).  Anything else is refused."""
+        check(lib().glu_sorted_search_set_option(self._h, name.encode(), value))
+
+    def index_ptr(self, hay_ptr, hay_count, key_type="uint32", stream=None):
+        """Builds the index of the haystack and remembers it for run_ptr(reuse_index=True) (glu_sorted_search_index_ptr)."""
+        check(lib().glu_sorted_search_index_ptr(self._h, _vp(hay_ptr), hay_count, KEY_TYPES[key_type], _vp(stream)))
+
+    def run_ptr(self, hay_ptr, hay_count, needles_ptr, needle_count, out_lower_ptr=None, out_upper_ptr=None, key_type="uint32",
+                reuse_index=False, stream=None):
+        """out_lower[j] = the keys of the haystack below needles[j], out_upper[j] = the keys not above it, in the sort's order;
+        either may be None.  All pointers are device pointers; the haystack and the needles are only read
+        (glu_sorted_search_run_ptr)."""
+        check(lib().glu_sorted_search_run_ptr(self._h, _vp(hay_ptr), hay_count, _vp(needles_ptr), needle_count, KEY_TYPES[key_type],
+                                              _vp(out_lower_ptr), _vp(out_upper_ptr), 1 if reuse_index else 0, _vp(stream)))
+
+    def last(self):
+        """(path, levels, kernels) of what the last index_ptr or run_ptr enqueued (glu_sorted_search_last; no device read)."""
+        a, b, c = _u32(), _u32(), _u32()
+        check(lib().glu_sorted_search_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_sorted_search_destroy(self._h)
         self._h = _vp()
 
     def __del__(self):

@@ -626,6 +626,83 @@ GLU_API glu_status glu_select_run_ptr(glu_select select, const void* stencil, in
  * rounds the one workgroup that scans the tile counts makes (4096 counts each).  Any pointer may be NULL. */
 GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds);
 
+/* ---- sorted search (not in the reference): the lower and the upper bound of many needles in a sorted haystack, what
+ * numpy.searchsorted is, on the device and on the caller's stream.  A join against the unique keys of key runs, a membership
+ * test, a histogram over arbitrary sorted bin edges, the rank of a value in a sorted array.
+ *   - `hay`: hay_count keys of one of the six glu_key_type's, sorted in the order glu_radix_sort_run_typed_ptr produces.  For
+ *     floats that is the TOTAL ORDER ON BITS: -0.0 < +0.0, and the NaNs lie beyond the infinities of their sign, ordered by
+ *     their payloads.  This is deliberately the SORT'S order and NOT the IEEE comparison of select (glu_select_run_ptr): a
+ *     position in a sorted array means what the sort made of it.  `needles`: needle_count keys of the same type, in any order.
+ *   - With enc the encoding the sort gives a key (unsigned, in the sort's order):
+ *       out_lower[j] = the number of i with enc(hay[i]) <  enc(needles[j])
+ *       out_upper[j] = the number of i with enc(hay[i]) <= enc(needles[j])
+ *     Both are device uint32_t[needle_count]; either may be NULL, not both; every entry is written.  A needle is in the
+ *     haystack iff upper > lower, and hay[lower .. upper) are its copies.  `hay` and `needles` are READ ONLY.
+ *   - hay_count == 0: every output is 0 and NULL hay is accepted.  needle_count == 0: nothing is enqueued beyond what the index
+ *     needs.
+ *   - Limits: hay_count < 2^32 and needle_count < 2^32; hay and needles aligned to the key size, the outputs to 4 bytes.
+ *   - A `hay` that is NOT SORTED gives unspecified positions in [0, hay_count] and never a read outside the arrays: every probe
+ *     index is clamped to the range it searches.
+ *   - TWO PATHS, chosen on the host from the counts and an option, never from the data:
+ *       DIRECT   a branch-free binary search of the haystack in global memory, ceil(log2(hay_count + 1)) probes for every
+ *                needle (a trip count that is the same for the whole kernel), one needle per lane.  One kernel.  Few needles, short
+ *                haystacks.
+ *       INDEXED  an index of F-ary samples of the haystack, F = 128 / sizeof(key) keys to the 128-byte line (32 or 16): level k
+ *                holds len_k = floor(hay_count / F^k) encoded keys, level_k[t] = enc(hay[(t + 1) * F^k - 1]), up to the first
+ *                level L with len_L <= TOP_ENTRIES, which the search kernel keeps in LDS.  A needle is searched in LDS and then
+ *                in ONE line per level, L lines in all, the haystack's among them.  The index holds fewer than
+ *                hay_count / (F - 1) keys and lives in the object's grow-only scratch, every level from a 128-byte boundary;
+ *                building it is one kernel that reads one key of every line of the haystack.  L == 0 (hay_count <= TOP_ENTRIES) has no
+ *                index: the call is DIRECT.
+ *     GLU_SEARCH_PATH_AUTO (the default) takes INDEXED iff L >= 1 and needle_count * 128 >= hay_count.  A call that builds the
+ *     index enqueues two kernels, every other call one.
+ *   - glu_sorted_search_index_ptr builds the index of a haystack and remembers (hay, hay_count, key_type, TOP_ENTRIES).
+ *     glu_sorted_search_run_ptr on the INDEXED path without reuse_index builds it again and remembers it too.  reuse_index != 0
+ *     is the caller's PROMISE that the haystack has not changed since: the call takes INDEXED whatever the needle count and
+ *     enqueues only the search kernel; GLU_ERROR_INVALID_STATE if no index was built or if one of the four remembered values
+ *     differs from the call's.
+ *   - glu_sorted_search_set_option: "PATH" = GLU_SEARCH_PATH_AUTO, _DIRECT or _INDEXED (INDEXED with L == 0 still runs DIRECT);
+ *     "TOP_ENTRIES" = the most entries of the top level, from F up to what LDS holds (8192 4-byte or 4096 8-byte keys, the
+ *     default; a call refuses a value outside the range of its own key width).  Any other name, or a value out of range, is
+ *     GLU_ERROR_INVALID_ARGUMENT.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: NULL search; NULL hay
+ *     with hay_count > 0; NULL needles with needle_count > 0; both outputs NULL; misalignment; a bad key type; the limits above;
+ *     an output overlapping hay, needles or the other output (arrays that merely touch are fine).  A refused call writes nothing.
+ *   - The calls only enqueue on `stream`: no host synchronisation, no side stream, no read-back, no atomics, nothing that waits
+ *     for another workgroup, and no device allocation once glu_sorted_search_prepare covered the haystack (else grow-only
+ *     allocation inside the call: not capturable; scratch that grows forgets the remembered index).  The kernels and their grids
+ *     follow from the counts and the addresses, so a captured call replays on any contents.
+ *   - OUT OF SCOPE: a haystack length that lives on the device (the idiom for the unique keys of key runs: pre-fill
+ *     unique_keys[0 .. max_runs) with the type's largest key and search all max_runs entries); a segmented search; a special
+ *     path for sorted needles (neighbouring lanes already share their lines); a merge. */
+typedef struct glu_sorted_search_s* glu_sorted_search;
+enum
+{
+    GLU_SEARCH_PATH_AUTO = 0,
+    GLU_SEARCH_PATH_DIRECT = 1,
+    GLU_SEARCH_PATH_INDEXED = 2
+};
+GLU_API glu_status glu_sorted_search_create(glu_sorted_search* out);
+GLU_API glu_status glu_sorted_search_destroy(glu_sorted_search search);
+/* Grow-only scratch for the index of `hay_count` (< 2^32) keys of `key_type` at the TOP_ENTRIES set now, so that the calls below
+ * allocate nothing (and can be captured). */
+GLU_API glu_status glu_sorted_search_prepare(glu_sorted_search search, size_t hay_count, glu_key_type key_type);
+GLU_API glu_status glu_sorted_search_set_option(glu_sorted_search search, const char* name, long long value);
+GLU_API glu_status glu_sorted_search_index_ptr(glu_sorted_search search, const void* hay, size_t hay_count, glu_key_type key_type,
+                                               void* stream);
+GLU_API glu_status glu_sorted_search_run_ptr(glu_sorted_search search, const void* hay, size_t hay_count, const void* needles,
+                                             size_t needle_count, glu_key_type key_type, uint32_t* out_lower, uint32_t* out_upper,
+                                             int reuse_index, void* stream);
+/* Host only, no device: what a call with these counts does under GLU_SEARCH_PATH_AUTO.  top_entries 0: the default.  path =
+ * GLU_SEARCH_PATH_DIRECT or _INDEXED; levels = L of the level rule above, whatever the path; fanout = F; index_bytes = the
+ * scratch of the L levels, sum over k = 1 .. L of len_k * sizeof(key) rounded up to 128 (what prepare reserves).  Any pointer
+ * may be NULL. */
+GLU_API glu_status glu_sorted_search_plan(size_t hay_count, size_t needle_count, glu_key_type key_type, uint32_t top_entries,
+                                          uint32_t* path, uint32_t* levels, uint32_t* fanout, size_t* index_bytes);
+/* What the host enqueued in the object's last index_ptr or run_ptr (no device read): the path taken, the levels of the index
+ * used (0 on the DIRECT path), the number of kernels. */
+GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* path, uint32_t* levels, uint32_t* kernels);
+
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
  * sharded form of glu::RadixSort::operator() (glu/RadixSort.hpp:273-334) that BASELINE.json configs[3] asks for.
