@@ -124,6 +124,12 @@ SYMBOLS = [
     ("glu_sorted_search_run_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _int, _vp]),
     ("glu_sorted_search_plan", _int, [_sz, _sz, _int, _u32, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_sorted_search_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_merge_create", _int, [_P(_vp)]),
+    ("glu_merge_destroy", _int, [_vp]),
+    ("glu_merge_prepare", _int, [_vp, _sz, _int]),
+    ("glu_merge_run_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
+    ("glu_merge_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_merge_last", _int, [_vp, _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -333,6 +339,15 @@ def plan_sorted_search(hay_count, needle_count, key_type="uint32", top_entries=0
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_sorted_search_plan(hay_count, needle_count, KEY_TYPES[key_type], top_entries, ctypes.byref(a), ctypes.byref(b),
                                        ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def plan_merge(a_count, b_count, key_type="uint32", with_vals=True):
+    """(tile, tiles, kernels, scratch_bytes) of a merge of `a_count` and `b_count` keys (glu_merge_plan; host only): the outputs per
+    workgroup, ceil((a_count + b_count) / tile), 2 kernels (0 for nothing), the bytes of the split table."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_merge_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b),
+                               ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
 
 
@@ -636,6 +651,42 @@ class SortedSearch:
     def destroy(self):
         if self._h and _lib is not None:
             _lib.glu_sorted_search_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Merge:
+    """glu::Merge (not in the reference) over the C ABI: two sorted arrays of keys, with or without uint32 values, into one, stable."""
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_merge_create(ctypes.byref(self._h)))
+
+    def prepare(self, total_count, key_type="uint32"):
+        """Scratch for calls of up to `total_count` = a_count + b_count keys: they allocate nothing (capturable) (glu_merge_prepare)."""
+        check(lib().glu_merge_prepare(self._h, total_count, KEY_TYPES[key_type]))
+
+    def run_ptr(self, a_keys_ptr, a_vals_ptr, a_count, b_keys_ptr, b_vals_ptr, b_count, out_keys_ptr, out_vals_ptr, key_type="uint32",
+                stream=None):
+        """out = the stable sort of A || B by the sort's order of keys, A first among equal keys; both inputs sorted in that order and
+        only read.  All pointers are device pointers; the three value pointers are all None or all set (glu_merge_run_ptr)."""
+        check(lib().glu_merge_run_ptr(self._h, _vp(a_keys_ptr), _vp(a_vals_ptr), a_count, _vp(b_keys_ptr), _vp(b_vals_ptr), b_count,
+                                      _vp(out_keys_ptr), _vp(out_vals_ptr), KEY_TYPES[key_type], _vp(stream)))
+
+    def last(self):
+        """(tiles, kernels) of what the last run_ptr enqueued (glu_merge_last; no device read)."""
+        a, b = _u32(), _u32()
+        check(lib().glu_merge_last(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_merge_destroy(self._h)
         self._h = _vp()
 
     def __del__(self):

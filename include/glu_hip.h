@@ -674,7 +674,7 @@ GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* til
  *     follow from the counts and the addresses, so a captured call replays on any contents.
  *   - OUT OF SCOPE: a haystack length that lives on the device (the idiom for the unique keys of key runs: pre-fill
  *     unique_keys[0 .. max_runs) with the type's largest key and search all max_runs entries); a segmented search; a special
- *     path for sorted needles (neighbouring lanes already share their lines); a merge. */
+ *     path for sorted needles (neighbouring lanes already share their lines). */
 typedef struct glu_sorted_search_s* glu_sorted_search;
 enum
 {
@@ -702,6 +702,55 @@ GLU_API glu_status glu_sorted_search_plan(size_t hay_count, size_t needle_count,
 /* What the host enqueued in the object's last index_ptr or run_ptr (no device read): the path taken, the levels of the index
  * used (0 on the DIRECT path), the number of kernels. */
 GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* path, uint32_t* levels, uint32_t* kernels);
+
+/* ---- merge (not in the reference): two sorted arrays of keys, with or without 4-byte values, into one sorted array, stable, on
+ * the device and on the caller's stream.  The update of a sorted table by a sorted batch, and the step between the batched or the
+ * sharded sorts and one sorted array (a merge tree is repeated calls).  It moves every pair once: 16 bytes a pair for 4-byte keys
+ * with values, 24 for 8-byte keys.
+ *   - out = the STABLE SORT OF THE CONCATENATION A || B BY enc(key), enc being the encoding the sort gives a key: the order
+ *     glu_radix_sort_run_typed_ptr produces and glu_sorted_search_run_ptr assumes (floats by their bits: -0.0 < +0.0, the NaNs
+ *     beyond the infinities, ordered by payload).  Both inputs must be sorted in that order.  Among equal keys every element of A
+ *     comes before every element of B, and each side keeps its own order:
+ *       A[i] lands at i + the number of j with enc(B[j]) <  enc(A[i])      (sorted search's lower bound)
+ *       B[j] lands at j + the number of i with enc(A[i]) <= enc(B[j])      (its upper bound)
+ *     Keys are copied bit for bit; values are uint32_t like the sort's and follow their keys.
+ *   - All six glu_key_type's.  a_count + b_count <= 2^32 - 1.
+ *   - a_vals, b_vals and out_vals are all NULL (keys only) or all non-NULL.  A side of count 0 is not looked at: its pointers may be
+ *     NULL.
+ *   - The inputs are READ ONLY.  out_keys and out_vals must not overlap any input range or each other (arrays that merely touch are
+ *     fine).  Every array may start at any multiple of its element size.
+ *   - Two kernels when a_count + b_count > 0, none otherwise: merge path.  The first finds, for every tile boundary of the output,
+ *     how many of the outputs in front of it come from A (a binary search over both inputs, (tiles + 1) words of the object's
+ *     scratch); the second merges one tile per workgroup in LDS and writes it with contiguous lanes.  No atomics, no look-back, no
+ *     side stream, no host synchronisation, and no device allocation once glu_merge_prepare covered the total (else grow-only
+ *     allocation inside the call: not capturable).  The kernels and their grids follow from the counts and the addresses, so a
+ *     captured call (one stream, no parallel branches) replays on any contents.
+ *   - An input that is NOT SORTED gives unspecified output CONTENTS; the call still writes exactly out[0 .. a_count + b_count) and
+ *     never reads or writes outside the six arrays (every probe of the searches is clamped, every tile's ranges are clamped).
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: NULL merge; a NULL key
+ *     pointer of a side with elements; a mix of NULL and non-NULL value pointers; misalignment; a bad key type; the limit above; an
+ *     output overlapping an input or the other output.  A refused call writes nothing.
+ *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge an
+ *     iota and gather); set operations; a segmented merge; counts that live on the device. */
+typedef struct glu_merge_s* glu_merge;
+/* Not in the reference. */
+GLU_API glu_status glu_merge_create(glu_merge* out);
+/* Not in the reference. */
+GLU_API glu_status glu_merge_destroy(glu_merge merge);
+/* Not in the reference.  Grow-only scratch (the split table) for calls with a_count + b_count <= total_count keys of `key_type`,
+ * with or without values: after it a call allocates nothing (and can be captured). */
+GLU_API glu_status glu_merge_prepare(glu_merge merge, size_t total_count, glu_key_type key_type);
+/* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const uint32_t* a_vals, size_t a_count, const void* b_keys,
+                                     const uint32_t* b_vals, size_t b_count, void* out_keys, uint32_t* out_vals, glu_key_type key_type,
+                                     void* stream);
+/* Not in the reference.  Host only, no device, pure: tile = outputs per workgroup (256 threads x 11 for 4-byte keys, x 7 for
+ * 8-byte keys, with and without values), tiles = ceil((a_count + b_count) / tile), kernels = 2 (0 if there is nothing to merge),
+ * scratch_bytes = (tiles + 1) * 4 (0 if there is nothing to merge): what prepare reserves.  Any pointer may be NULL. */
+GLU_API glu_status glu_merge_plan(size_t a_count, size_t b_count, glu_key_type key_type, int with_vals, uint32_t* tile, uint32_t* tiles,
+                                  uint32_t* kernels, size_t* scratch_bytes);
+/* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
+GLU_API glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
