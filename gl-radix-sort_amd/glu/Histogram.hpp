@@ -1,0 +1,99 @@
+// glu/Histogram.hpp -- glu::Histogram on MI355X (not in the reference): how many samples fall into each bin, over even bins or over
+// sorted bin edges; numpy.histogram, torch.histc and torch.bincount on the device.
+#ifndef GLU_HISTOGRAM_HPP
+#define GLU_HISTOGRAM_HPP
+
+#include <type_traits>
+
+#include "hip_utils.hpp"
+
+namespace glu
+{
+    /// out_counts[b] = the samples of bin b, uint32.  Everything stays on the device; the work is enqueued, not waited for
+    /// (glu_histogram_run_even_ptr and glu_histogram_run_edges_ptr in glu_hip.h).  The same input gives the same bits every time.
+    class Histogram
+    {
+    public:
+        Histogram() { GLU_CHECK_STATUS(glu_histogram_create(&m_impl)); }
+
+        Histogram(const Histogram&) = delete;
+        Histogram& operator=(const Histogram&) = delete;
+
+        ~Histogram() { glu_histogram_destroy(m_impl); }
+
+        /// Scratch for calls of up to `count` samples and `bins` bins: they then allocate nothing and can be captured.
+        void prepare(size_t count, size_t bins) { GLU_CHECK_STATUS(glu_histogram_prepare(m_impl, count, bins)); }
+
+        /// `bins` even bins over [lo, hi); lo and hi are values of the sample's type (uint32_t, int32_t, float or double) on the
+        /// host.  Integers: (hi - lo) / bins must be a whole number, and the bin is exact.  accumulate: add to out_counts.
+        template<typename T>
+        void even(const T* device_samples, size_t count, T lo, T hi, size_t bins, uint32_t* device_out_counts, bool accumulate = false,
+                  void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_even_ptr(m_impl, device_samples, count, key_type_of<T>(), &lo, &hi, bins, device_out_counts,
+                                                        accumulate ? 1 : 0, stream));
+        }
+
+        /// Bins between `bins + 1` non-decreasing device edges of the sample's type: bin b holds edges[b] <= x < edges[b + 1].
+        template<typename T>
+        void edges(const T* device_samples, size_t count, const T* device_edges, size_t bins, uint32_t* device_out_counts,
+                   bool accumulate = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_edges_ptr(m_impl, device_samples, count, key_type_of<T>(), device_edges, bins,
+                                                         device_out_counts, accumulate ? 1 : 0, stream));
+        }
+
+        /// out_counts[v] = the ids equal to v, v < bins (ids of `bins` and more are not counted).
+        void bincount(const uint32_t* device_ids, size_t count, size_t bins, uint32_t* device_out_counts, bool accumulate = false,
+                      void* stream = nullptr)
+        {
+            even<uint32_t>(device_ids, count, 0u, (uint32_t) bins, bins, device_out_counts, accumulate, stream);
+        }
+
+        /// uint32 ids in a buffer, from its start.
+        void bincount(const ShaderStorageBuffer& ids, size_t count, size_t bins, ShaderStorageBuffer& out_counts, bool accumulate = false)
+        {
+            bincount((const uint32_t*) ids.device_ptr(), count, bins, (uint32_t*) out_counts.device_ptr(), accumulate);
+        }
+
+        /// What a call with these counts does (glu_histogram_plan; host only, no device needed).
+        struct Plan
+        {
+            uint32_t path = 0, threads = 0, tile = 0, groups = 0, kernels = 0;
+            size_t scratch_bytes = 0;
+        };
+        [[nodiscard]] static Plan plan(size_t count, size_t bins, glu_key_type key_type = GLU_KEY_UINT32, int mode = GLU_HISTOGRAM_EVEN)
+        {
+            Plan p;
+            GLU_CHECK_STATUS(glu_histogram_plan(count, bins, key_type, mode, &p.path, &p.threads, &p.tile, &p.groups, &p.kernels, &p.scratch_bytes));
+            return p;
+        }
+
+        /// What the last call enqueued: the path, the workgroups of the counting kernel and the number of kernels.
+        struct Last
+        {
+            uint32_t path = 0, groups = 0, kernels = 0;
+        };
+        [[nodiscard]] Last last() const
+        {
+            Last l;
+            GLU_CHECK_STATUS(glu_histogram_last(m_impl, &l.path, &l.groups, &l.kernels));
+            return l;
+        }
+
+    private:
+        template<typename T>
+        static constexpr glu_key_type key_type_of()
+        {
+            static_assert(sizeof(T) == 4 || sizeof(T) == 8, "samples are 4 or 8 bytes wide");
+            if constexpr (sizeof(T) == 4)
+                return std::is_floating_point<T>::value ? GLU_KEY_FLOAT32 : std::is_signed<T>::value ? GLU_KEY_INT32 : GLU_KEY_UINT32;
+            else
+                return std::is_floating_point<T>::value ? GLU_KEY_FLOAT64 : std::is_signed<T>::value ? GLU_KEY_INT64 : GLU_KEY_UINT64;
+        }
+
+        glu_histogram m_impl = nullptr;
+    };
+} // namespace glu
+
+#endif // GLU_HISTOGRAM_HPP

@@ -130,6 +130,13 @@ SYMBOLS = [
     ("glu_merge_run_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
     ("glu_merge_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_merge_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_histogram_create", _int, [_P(_vp)]),
+    ("glu_histogram_destroy", _int, [_vp]),
+    ("glu_histogram_prepare", _int, [_vp, _sz, _sz]),
+    ("glu_histogram_run_even_ptr", _int, [_vp, _vp, _sz, _int, _vp, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_run_edges_ptr", _int, [_vp, _vp, _sz, _int, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_histogram_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -349,6 +356,21 @@ def plan_merge(a_count, b_count, key_type="uint32", with_vals=True):
     check(lib().glu_merge_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b),
                                ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
+
+
+HistogramMode_Even, HistogramMode_Edges = 0, 1
+HistogramPath_Lds, HistogramPath_Global = 0, 1
+HISTOGRAM_MODES = {"even": HistogramMode_Even, "edges": HistogramMode_Edges}
+
+
+def plan_histogram(count, bins, key_type="uint32", mode="even"):
+    """(path, threads, tile, groups, kernels, scratch_bytes) of a histogram of `count` samples over `bins` bins (glu_histogram_plan;
+    host only): HistogramPath_Lds where bins <= 8192 else HistogramPath_Global, the workgroup and the tile of the counting kernel,
+    its workgroups min(ceil(count / tile), groups_max), the kernels of a call that does not accumulate, the bytes of the partial rows."""
+    a, b, c, d, e, f = _u32(), _u32(), _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_histogram_plan(count, bins, KEY_TYPES[key_type], HISTOGRAM_MODES.get(mode, mode), ctypes.byref(a), ctypes.byref(b),
+                                   ctypes.byref(c), ctypes.byref(d), ctypes.byref(e), ctypes.byref(f)))
+    return a.value, b.value, c.value, d.value, e.value, f.value
 
 
 def _read_batch(fn, handle):
@@ -687,6 +709,62 @@ class Merge:
     def destroy(self):
         if self._h and _lib is not None:
             _lib.glu_merge_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+_HISTOGRAM_BOUNDS = {"uint32": ctypes.c_uint32, "int32": ctypes.c_int32, "float32": ctypes.c_float, "float64": ctypes.c_double,
+                     "uint64": ctypes.c_uint64, "int64": ctypes.c_int64}
+
+
+class Histogram:
+    """glu::Histogram (not in the reference) over the C ABI: uint32 counts of the samples per bin, over even bins or sorted edges."""
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_histogram_create(ctypes.byref(self._h)))
+
+    def prepare(self, count, bins):
+        """Scratch for calls of up to `count` samples and `bins` bins: they allocate nothing (capturable) (glu_histogram_prepare)."""
+        check(lib().glu_histogram_prepare(self._h, count, bins))
+
+    def run_even_ptr(self, samples_ptr, count, lo, hi, bins, out_counts_ptr, key_type="uint32", accumulate=False, stream=None):
+        """`bins` even bins over [lo, hi).  lo and hi are Python numbers: integers that the sample's type holds (others are refused),
+        floats rounded to the sample's type (for float32 samples lo = 0.1 means np.float32(0.1), which the kernels widen to double).
+        Integers: (hi - lo) / bins a whole number, the bin exact; floats: min(uint32((double(x) - lo) * (bins / (hi - lo))),
+        bins - 1).  lo = 0, hi = bins over uint32 is bincount.  Pointers are device pointers (glu_histogram_run_even_ptr)."""
+        c = _HISTOGRAM_BOUNDS[key_type]
+        try:
+            lo_v, hi_v = c(lo), c(hi)
+        except TypeError:  # (a fraction for an integer type)
+            raise GluError(GLU_ERROR_INVALID_ARGUMENT, "lo or hi is not a value of %s: %r, %r" % (key_type, lo, hi))
+        # (a float32 bound is rounded to float32, as numpy rounds a Python float it stores in a float32 array; an integer bound that
+        # the type does not hold is refused, not wrapped)
+        if key_type in ("uint32", "int32", "uint64", "int64") and (lo_v.value != lo or hi_v.value != hi):
+            raise GluError(GLU_ERROR_INVALID_ARGUMENT, "lo or hi is not a value of %s: %r, %r" % (key_type, lo, hi))
+        check(lib().glu_histogram_run_even_ptr(self._h, _vp(samples_ptr), count, KEY_TYPES[key_type], ctypes.byref(lo_v), ctypes.byref(hi_v),
+                                               bins, _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+
+    def run_edges_ptr(self, samples_ptr, count, edges_ptr, bins, out_counts_ptr, key_type="uint32", accumulate=False, stream=None):
+        """Bins between the bins + 1 non-decreasing DEVICE edges of the sample's type: bin b counts edges[b] <= x < edges[b + 1], floats
+        as IEEE values (NaN samples dropped) (glu_histogram_run_edges_ptr)."""
+        check(lib().glu_histogram_run_edges_ptr(self._h, _vp(samples_ptr), count, KEY_TYPES[key_type], _vp(edges_ptr), bins,
+                                                _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+
+    def last(self):
+        """(path, groups, kernels) of what the last run enqueued (glu_histogram_last; no device read)."""
+        a, b, c = _u32(), _u32(), _u32()
+        check(lib().glu_histogram_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_histogram_destroy(self._h)
         self._h = _vp()
 
     def __del__(self):

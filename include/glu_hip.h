@@ -628,7 +628,8 @@ GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* til
 
 /* ---- sorted search (not in the reference): the lower and the upper bound of many needles in a sorted haystack, what
  * numpy.searchsorted is, on the device and on the caller's stream.  A join against the unique keys of key runs, a membership
- * test, a histogram over arbitrary sorted bin edges, the rank of a value in a sorted array.
+ * test, the bin index of every sample over arbitrary sorted bin edges (the COUNTS per bin are glu_histogram_run_edges_ptr), the
+ * rank of a value in a sorted array.
  *   - `hay`: hay_count keys of one of the six glu_key_type's, sorted in the order glu_radix_sort_run_typed_ptr produces.  For
  *     floats that is the TOTAL ORDER ON BITS: -0.0 < +0.0, and the NaNs lie beyond the infinities of their sign, ordered by
  *     their payloads.  This is deliberately the SORT'S order and NOT the IEEE comparison of select (glu_select_run_ptr): a
@@ -751,6 +752,92 @@ GLU_API glu_status glu_merge_plan(size_t a_count, size_t b_count, glu_key_type k
                                   uint32_t* kernels, size_t* scratch_bytes);
 /* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
 GLU_API glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels);
+
+/* ---- histogram (not in the reference): how many samples fall into each bin, over even bins (numpy.histogram with a range,
+ * torch.histc, torch.bincount) or over sorted bin edges (numpy.histogram with edges), on the device and on the caller's stream.
+ * One read of the samples, 4 or 8 bytes a sample; nothing per sample is written.
+ *   - TYPES.  Samples are the six glu_key_type's.  Counts are uint32_t out_counts[bins] on the device; every entry is written.
+ *   - ARGUMENTS.  count < 2^32.  `samples` is READ ONLY and aligned to its element size; out_counts is aligned to 4 bytes.
+ *     accumulate != 0 adds the call's counts to what out_counts holds, modulo 2^32; with accumulate == 0 the call overwrites and the
+ *     prior contents do not matter.  count == 0 is legal with NULL samples: all zeros, or nothing touched under accumulate.
+ *   - EVEN BINS, glu_histogram_run_even_ptr.  `lo` and `hi` are HOST pointers to one value each of the sample's type, read during
+ *     the call and passed to the kernels by value (as select passes its threshold), so the call stays capturable.  A sample counts
+ *     iff lo <= x < hi.  1 <= bins <= 2^24.
+ *       UINT32, INT32: W = ((int64) hi - lo) / bins must be a whole number >= 1, else the call is an invalid argument (uneven or
+ *         fractional widths: pass edges).  bin = floor((x - lo) / W) EXACTLY, for every x in range: the kernels multiply by
+ *         ceil(2^64 / W) and keep the top 64 bits of the 96-bit product, which is the quotient for every 32-bit dividend
+ *         (histogram_bins.hpp has the proof), not a reciprocal that can be one off beside a multiple of W.  lo = 0, hi = bins is
+ *         bincount.
+ *       FLOAT32, FLOAT64: lo and hi finite, lo < hi, hi - lo and bins / (hi - lo) finite in double.  With d = (double) x, a NaN is
+ *         dropped and d must satisfy lo <= d < hi; bin = min((uint32) ((d - lo) * scale), bins - 1) with
+ *         scale = (double) bins / ((double) hi - (double) lo) computed once on the host: one subtraction and one multiplication in
+ *         IEEE double, nothing that could contract into an FMA, no fast-math, so numpy restates it bit for bit.
+ *       UINT64, INT64: an invalid argument here (their even bins are not exact in double): pass edges.
+ *   - SORTED EDGES, glu_histogram_run_edges_ptr.  `edges` is a DEVICE array of bins + 1 values of the sample's type,
+ *     non-decreasing.  1 <= bins <= 8192.  bin = (the number of e in edges with e <= x) - 1; the sample counts iff
+ *     0 <= bin < bins, that is iff edges[0] <= x < edges[bins].  Floats compare as IEEE VALUES, as in select and in numpy:
+ *     -0.0 == +0.0, and a NaN sample fails every comparison and is dropped.  This is deliberately NOT the order on bits of the sort
+ *     and of sorted search (glu_sorted_search_run_ptr): a bin is a range of values, not a position in a sorted array.  Repeated
+ *     edges make empty bins.  Edges that hold a NaN or are not non-decreasing give unspecified counts and never an access outside
+ *     the arrays: the search is clamped and the bin is checked against `bins` before it is used.  More than 8192 uneven bins are
+ *     OUT OF SCOPE; the way round: sort the samples, search the edges in them (glu_sorted_search_run_ptr), difference the bounds.
+ *   - TWO PATHS, chosen from `bins`, never from the data (glu_histogram_plan states them).
+ *       GLU_HISTOGRAM_PATH_LDS, bins <= 8192, both modes: kernel 1 runs groups = min(tiles, groups_max) workgroups, each with a
+ *         table of `bins` counters in LDS (edges mode: and the edges beside it), walks its tiles adding with LDS atomics, and stores
+ *         its table as row g of partial[groups][bins] in the object's scratch; kernel 2 sums the columns:
+ *         out[b] = (accumulate ? out[b] : 0) + the sum over g of partial[g][b].  Kernel 2 always runs unless count == 0 and
+ *         accumulate; with count == 0 it runs over zero rows, which writes the zeros.  No global atomics, no clearing pass.
+ *       GLU_HISTOGRAM_PATH_GLOBAL, bins > 8192, even bins only: one kernel clears out_counts (skipped under accumulate), one adds
+ *         with device-scope atomics straight into out_counts.  No scratch.
+ *     Skew: a wave whose counted samples of a tile all fall into one bin issues ONE add of their number, and holds that add back
+ *     while its following tiles fall into the same bin (one add per wave and call for input that is one value); a thread adds each
+ *     run of equal bins among its own samples once.  On the LDS path skew costs nothing.  On the GLOBAL path hot bins that meet in
+ *     neither rule serialise on their addresses (DESIGN.md 4.15 has the figures): skewed data wants at most 8192 bins.
+ *   - The calls only enqueue on `stream`: no host synchronisation, no side stream, no read-back, and no device allocation once
+ *     glu_histogram_prepare covered the counts (else grow-only allocation inside the call: not capturable).  Grids follow from the
+ *     counts and the addresses, never from the data: a captured call (one stream, no parallel branches) replays on any contents,
+ *     of the samples and of the device edges.
+ *   - Counts are integers, so the atomics do not make a result depend on the order of arrival: THE SAME INPUT GIVES THE SAME BITS
+ *     EVERY TIME.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument, and nothing written:
+ *     a NULL object; NULL samples with count > 0; NULL out_counts, lo, hi or edges; misalignment; a bad key type; the limits and
+ *     rules above; out_counts overlapping the samples or the edges (arrays that merely touch are fine).
+ *   - OUT OF SCOPE: weights, several channels, 2-D, 64-bit counts, a right-closed last bin. */
+typedef struct glu_histogram_s* glu_histogram;
+enum
+{
+    GLU_HISTOGRAM_EVEN = 0,
+    GLU_HISTOGRAM_EDGES = 1
+};
+enum
+{
+    GLU_HISTOGRAM_PATH_LDS = 0,
+    GLU_HISTOGRAM_PATH_GLOBAL = 1
+};
+/* Not in the reference. */
+GLU_API glu_status glu_histogram_create(glu_histogram* out);
+/* Not in the reference. */
+GLU_API glu_status glu_histogram_destroy(glu_histogram histogram);
+/* Not in the reference.  Grow-only scratch (the partial rows) for calls with up to `count` samples and `bins` bins, of any key type
+ * and either mode: after it such a call allocates nothing (and can be captured). */
+GLU_API glu_status glu_histogram_prepare(glu_histogram histogram, size_t count, size_t bins);
+/* Not in the reference.  The contract above, even bins.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_histogram_run_even_ptr(glu_histogram histogram, const void* samples, size_t count, glu_key_type key_type,
+                                              const void* lo, const void* hi, size_t bins, uint32_t* out_counts, int accumulate, void* stream);
+/* Not in the reference.  The contract above, sorted edges.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_histogram_run_edges_ptr(glu_histogram histogram, const void* samples, size_t count, glu_key_type key_type,
+                                               const void* edges, size_t bins, uint32_t* out_counts, int accumulate, void* stream);
+/* Not in the reference.  Host only, no device, pure.  mode = GLU_HISTOGRAM_EVEN or _EDGES.  path = _PATH_LDS where bins <= 8192,
+ * else _PATH_GLOBAL.  threads = the workgroup of the counting kernel: 256 for even bins, 512 for edges of 4-byte and 1024 for edges
+ * of 8-byte samples (16 waves to the CU beside 32, 64 and 96 KiB of LDS).  tile = threads x 4 packs of 16 bytes, in samples;
+ * groups = min(ceil(count / tile), groups_max), groups_max = 1024, 512, 256 in the same order; kernels = what a call with
+ * accumulate == 0 enqueues: 2, or 1 where count == 0 (under accumulate: one fewer on the GLOBAL path and where count == 0);
+ * scratch_bytes = groups * bins * 4 on the LDS path, 0 on the GLOBAL path.  Any pointer may be NULL. */
+GLU_API glu_status glu_histogram_plan(size_t count, size_t bins, glu_key_type key_type, int mode, uint32_t* path, uint32_t* threads,
+                                      uint32_t* tile, uint32_t* groups, uint32_t* kernels, size_t* scratch_bytes);
+/* Not in the reference.  What the host enqueued in the object's last run (no device read): the path, the workgroups of the counting
+ * kernel and the number of kernels. */
+GLU_API glu_status glu_histogram_last(glu_histogram histogram, uint32_t* path, uint32_t* groups, uint32_t* kernels);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
