@@ -137,6 +137,12 @@ SYMBOLS = [
     ("glu_histogram_run_edges_ptr", _int, [_vp, _vp, _sz, _int, _vp, _sz, _vp, _int, _vp]),
     ("glu_histogram_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_histogram_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_expand_create", _int, [_P(_vp)]),
+    ("glu_expand_destroy", _int, [_vp]),
+    ("glu_expand_prepare", _int, [_vp, _sz, _sz]),
+    ("glu_expand_run_ptr", _int, [_vp, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _vp, _vp]),
+    ("glu_expand_plan", _int, [_sz, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_expand_last", _int, [_vp, _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -371,6 +377,15 @@ def plan_histogram(count, bins, key_type="uint32", mode="even"):
     check(lib().glu_histogram_plan(count, bins, KEY_TYPES[key_type], HISTOGRAM_MODES.get(mode, mode), ctypes.byref(a), ctypes.byref(b),
                                    ctypes.byref(c), ctypes.byref(d), ctypes.byref(e), ctypes.byref(f)))
     return a.value, b.value, c.value, d.value, e.value, f.value
+
+
+def plan_expand(total, num_segments):
+    """(tile, tiles, kernels, scratch_bytes) of an expand of `num_segments` segments over `total` elements (glu_expand_plan; host
+    only): the merged items (offsets and outputs together) per workgroup, ceil((num_segments + 1 + total) / tile), 2 kernels and the
+    bytes of the split table; with no element or no segment, 0 tiles, kernels and bytes."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_expand_plan(total, num_segments, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
 
 
 def _read_batch(fn, handle):
@@ -765,6 +780,45 @@ class Histogram:
     def destroy(self):
         if self._h and _lib is not None:
             _lib.glu_histogram_destroy(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Expand:
+    """glu::Expand (not in the reference) over the C ABI: for every element the segment that holds it, its rank inside the segment
+    and the segment's item, from the offsets of the batched family.  The inverse of KeyRuns; numpy.repeat on the device."""
+
+    def __init__(self):
+        self._h = _vp()
+        check(lib().glu_expand_create(ctypes.byref(self._h)))
+
+    def prepare(self, total, num_segments):
+        """Scratch for calls of up to `total` elements and `num_segments` segments: they allocate nothing (capturable)
+        (glu_expand_prepare)."""
+        check(lib().glu_expand_prepare(self._h, total, num_segments))
+
+    def run_ptr(self, offsets_ptr, num_segments, total, out_segments_ptr=None, out_ranks_ptr=None, items_ptr=None, out_items_ptr=None,
+                item_bytes=4, stream=None):
+        """With s(j) = numpy.searchsorted(offsets, j, "right") - 1 for j < total, wherever 0 <= s(j) < num_segments:
+        out_segments[j] = s(j), out_ranks[j] = j - offsets[s(j)], out_items[j] = items[s(j)] (item_bytes 4, 8, 16 or 32); other
+        positions are not touched.  Every output is optional.  All pointers are device pointers (glu_expand_run_ptr)."""
+        check(lib().glu_expand_run_ptr(self._h, _vp(offsets_ptr), num_segments, total, _vp(items_ptr), item_bytes, _vp(out_items_ptr),
+                                       _vp(out_segments_ptr), _vp(out_ranks_ptr), _vp(stream)))
+
+    def last(self):
+        """(tiles, kernels) of what the last run_ptr enqueued (glu_expand_last; no device read)."""
+        a, b = _u32(), _u32()
+        check(lib().glu_expand_last(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def destroy(self):
+        if self._h and _lib is not None:
+            _lib.glu_expand_destroy(self._h)
         self._h = _vp()
 
     def __del__(self):

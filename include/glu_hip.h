@@ -731,8 +731,10 @@ GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* pa
  *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: NULL merge; a NULL key
  *     pointer of a side with elements; a mix of NULL and non-NULL value pointers; misalignment; a bad key type; the limit above; an
  *     output overlapping an input or the other output.  A refused call writes nothing.
- *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge an
- *     iota and gather); set operations; a segmented merge; counts that live on the device. */
+ *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge
+ *     an iota as the values, and fetch the wide values through the merged iota; the library has no gather by an arbitrary
+ *     permutation: glu_expand_run_ptr gathers per SEGMENT, out[j] = items[segment of j], which is that fetch only where the
+ *     merged iota is a sequence of runs); set operations; a segmented merge; counts that live on the device. */
 typedef struct glu_merge_s* glu_merge;
 /* Not in the reference. */
 GLU_API glu_status glu_merge_create(glu_merge* out);
@@ -838,6 +840,70 @@ GLU_API glu_status glu_histogram_plan(size_t count, size_t bins, glu_key_type ke
 /* Not in the reference.  What the host enqueued in the object's last run (no device read): the path, the workgroups of the counting
  * kernel and the number of kernels. */
 GLU_API glu_status glu_histogram_last(glu_histogram histogram, uint32_t* path, uint32_t* groups, uint32_t* kernels);
+
+/* ---- expand (not in the reference): from the offsets of segments back to the elements: for every element the segment that holds
+ * it, its rank inside that segment and the segment's item, on the device and on the caller's stream.  The inverse of key runs
+ * (glu_key_runs_run_ptr is a run-length encoder, this is the decoder), numpy.repeat / torch.repeat_interleave with device-resident
+ * counts, the broadcast of a per-segment result (a sum of glu_reduce_run_batch_offsets_ptr) onto the segment's elements, and the
+ * (needle, match) pairs of a join from glu_sorted_search_run_ptr's ranges.  It reads the offsets once and writes 4 bytes (an item:
+ * item_bytes) per element and requested output.
+ *   - `offsets` is the batched family's array: num_segments + 1 uint32_t on the device, non-decreasing, never read by the host.
+ *     `total` is the host-known length of the output arrays (what `count` is to the batched calls).
+ *   - For every j in [0, total): c(j) = the number of r in [0, num_segments] with offsets[r] <= j.  j is COVERED iff
+ *     1 <= c(j) <= num_segments, that is iff offsets[0] <= j < offsets[num_segments]; then s(j) = c(j) - 1, which is
+ *     numpy.searchsorted(offsets, j, side="right") - 1.  Empty segments, anywhere and in any number, are skipped by this rule.
+ *       out_segments[j] = s(j)
+ *       out_ranks[j]    = j - offsets[s(j)]
+ *       out_items[j]    = items[s(j)], copied bit for bit; item_bytes is 4, 8, 16 or 32 (select's sizes), `items` holds
+ *                         num_segments of them
+ *     Each output is optional (NULL skips it); items and out_items are both NULL or both given (item_bytes is ignored without).
+ *   - POSITIONS THAT ARE NOT COVERED ARE NOT TOUCHED (the batched family's rule).  Nothing at or behind `total` is written even
+ *     where offsets[num_segments] > total: the positions below total are written, the rest is dropped, and the caller finds the
+ *     true total in offsets[num_segments] (there is no count output).
+ *   - The counts form has no entry point: write the counts to counts[0 .. num_segments), any value behind them, and run
+ *     glu_scan_run_batch_offsets_ptr in place over the num_segments + 1 words as ONE segment; the exclusive sums are the offsets.
+ *   - Offsets that decrease or go beyond `total` give unspecified CONTENTS of [0, total) of the outputs, and never a write outside
+ *     [0, total) of the three outputs nor a read outside offsets[0 .. num_segments] and items[0 .. num_segments): every tile's
+ *     ranges are clamped, and the segment index of a gather is tested against num_segments, not trusted.
+ *   - total == 0 or num_segments == 0: nothing is enqueued, GLU_OK, and no array is looked at (all may be NULL).  With all three
+ *     outputs NULL nothing is enqueued either.
+ *   - num_segments <= 2^24, total < 2^32, total + num_segments + 1 <= 2^32 - 1.  offsets, out_segments and out_ranks are aligned to
+ *     4 bytes, items and out_items to min(item_bytes, 16).  `offsets` and `items` are READ ONLY; no output may overlap them or
+ *     another output (arrays that merely touch are fine).
+ *   - Two kernels: a load-balancing search, which is merge path between the offsets and the positions 0 .. total - 1 with the
+ *     offsets first on ties.  The first finds, for every tile boundary of that MERGED sequence of num_segments + 1 + total items,
+ *     how many offsets lie in front of it ((tiles + 1) words of the object's scratch); the second takes one tile per workgroup:
+ *     its offsets go to LDS, each marks the position it equals, a max-scan of the marks gives every position its segment, and the
+ *     outputs leave in whole 16-byte packs by contiguous lanes.  A tile holds at most `tile` offsets AND outputs together, so
+ *     millions of empty segments become tiles that write nothing, not one workgroup's loop.  No atomics, no look-back, no side
+ *     stream, no host synchronisation, no read-back, and no device allocation once glu_expand_prepare covered the sizes (else
+ *     grow-only allocation inside the call: not capturable).  The kernels and their grids follow from total, num_segments and the
+ *     addresses, never from the data: a captured call (one stream, no parallel branches) replays on any offsets.  THE SAME INPUT
+ *     GIVES THE SAME BITS EVERY TIME.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: a NULL object; NULL
+ *     offsets with work to do; only one of items and out_items; a bad item_bytes; misalignment; the limits above; an output
+ *     overlapping offsets, items or another output.  A refused call writes nothing.
+ *   - OUT OF SCOPE: a counts-form entry point (the recipe above); items wider than 32 bytes; a gather by an arbitrary permutation;
+ *     a segmented select that rewrites offsets; 64-bit offsets. */
+typedef struct glu_expand_s* glu_expand;
+/* Not in the reference. */
+GLU_API glu_status glu_expand_create(glu_expand* out);
+/* Not in the reference. */
+GLU_API glu_status glu_expand_destroy(glu_expand expand);
+/* Not in the reference.  Grow-only scratch (the split table) for calls of up to `total` elements and `num_segments` segments: after
+ * it such a call allocates nothing (and can be captured). */
+GLU_API glu_status glu_expand_prepare(glu_expand expand, size_t total, size_t num_segments);
+/* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_expand_run_ptr(glu_expand expand, const uint32_t* offsets, size_t num_segments, size_t total, const void* items,
+                                      uint32_t item_bytes, void* out_items, uint32_t* out_segments, uint32_t* out_ranks, void* stream);
+/* Not in the reference.  Host only, no device, pure: tile = merged items (offsets and outputs together) per workgroup, 256 threads
+ * x 11; tiles = ceil((num_segments + 1 + total) / tile); kernels = 2; scratch_bytes = (tiles + 1) * 4: what prepare reserves.
+ * With total == 0 or num_segments == 0 there is nothing to do: tiles, kernels and scratch_bytes are 0.  Any pointer may be NULL. */
+GLU_API glu_status glu_expand_plan(size_t total, size_t num_segments, uint32_t* tile, uint32_t* tiles, uint32_t* kernels,
+                                   size_t* scratch_bytes);
+/* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels (0 and 0
+ * where the call had nothing to do). */
+GLU_API glu_status glu_expand_last(glu_expand expand, uint32_t* tiles, uint32_t* kernels);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
