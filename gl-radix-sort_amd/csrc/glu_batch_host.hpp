@@ -30,8 +30,7 @@ inline glu_status check_batch_segments(size_t num_segments)
 inline glu_status check_batch_offsets(const uint32_t* offsets, size_t num_segments)
 {
     if (num_segments && !offsets) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid offsets array");
-    if ((uintptr_t) offsets % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the offsets array is not aligned to its element size");
-    return GLU_OK;
+    return check_aligned(offsets, sizeof(uint32_t), "the offsets array", "its element size");
 }
 
 // the list image of a batch, reserved: the line of counts, then the lists of `layout`
@@ -89,9 +88,9 @@ struct LastBatch
             for (int c = 0; c < BATCH_LIST_LONG; c++) out[c < wave_lists ? 0 : 1] += counts[c];
             out[2] = counts[kBatchCountLong];
         }
-        if (wave_segments) *wave_segments = out[0];
-        if (block_segments) *block_segments = out[1];
-        if (long_segments) *long_segments = out[2];
+        store(wave_segments, out[0]);
+        store(block_segments, out[1]);
+        store(long_segments, out[2]);
         return GLU_OK;
     }
 };

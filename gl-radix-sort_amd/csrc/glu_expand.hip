@@ -39,35 +39,21 @@ glu_status glu_expand_plan(size_t total, size_t num_segments, uint32_t* tile, ui
 {
     GLU_TRY(check_sizes(total, num_segments));
     const ExpandPlan p = expand_plan(total, num_segments);
-    if (tile) *tile = p.tile;
-    if (tiles) *tiles = p.tiles;
-    if (kernels) *kernels = p.kernels;
-    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(kernels, p.kernels);
+    store(scratch_bytes, p.scratch_bytes);
     return GLU_OK;
 }
 
-glu_status glu_expand_create(glu_expand* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_expand_s();
-    return GLU_OK;
-}
+glu_status glu_expand_create(glu_expand* out) { return create_object(out); }
 
-glu_status glu_expand_destroy(glu_expand expand)
-{
-    GLU_TRY(enter());
-    if (!expand) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    expand->split.release();
-    delete expand;
-    return GLU_OK;
-}
+glu_status glu_expand_destroy(glu_expand expand) { return destroy_object(expand); }
 
 glu_status glu_expand_prepare(glu_expand expand, size_t total, size_t num_segments)
 {
     GLU_TRY(enter());
-    if (!expand) return fail(GLU_ERROR_INVALID_ARGUMENT, "expand is NULL");
+    GLU_TRY(check_not_null(expand, "expand"));
     GLU_TRY(check_sizes(total, num_segments));
     return expand->split.reserve(expand_plan(total, num_segments).scratch_bytes);
 }
@@ -76,7 +62,7 @@ glu_status glu_expand_run_ptr(glu_expand expand, const uint32_t* offsets, size_t
                               uint32_t item_bytes, void* out_items, uint32_t* out_segments, uint32_t* out_ranks, void* stream)
 {
     GLU_TRY(enter());
-    if (!expand) return fail(GLU_ERROR_INVALID_ARGUMENT, "expand is NULL");
+    GLU_TRY(check_not_null(expand, "expand"));
     GLU_TRY(check_sizes(total, num_segments));
     ExpandPlan p = expand_plan(total, num_segments);
     if (!p.kernels) // no position or no segment: no array is looked at
@@ -87,30 +73,15 @@ glu_status glu_expand_run_ptr(glu_expand expand, const uint32_t* offsets, size_t
     if (!offsets) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid offsets buffer");
     if ((items != nullptr) != (out_items != nullptr))
         return fail(GLU_ERROR_INVALID_ARGUMENT, "items and out_items must be both NULL (no gather) or both non-NULL");
-    if (items && item_bytes != 4 && item_bytes != 8 && item_bytes != 16 && item_bytes != 32)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "item_bytes must be 4, 8, 16 or 32 (got %u)", item_bytes);
+    if (items) GLU_TRY(check_item_bytes(item_bytes));
     if (!items) item_bytes = 0;
-    const uint32_t item_align = item_bytes < 16 ? item_bytes : 16u;
-    if ((uintptr_t) offsets % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "offsets is not aligned to 4 bytes");
-    if ((uintptr_t) out_segments % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_segments is not aligned to 4 bytes");
-    if ((uintptr_t) out_ranks % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_ranks is not aligned to 4 bytes");
-    if (items && (uintptr_t) items % item_align) return fail(GLU_ERROR_INVALID_ARGUMENT, "items is not aligned to %u bytes", item_align);
-    if (items && (uintptr_t) out_items % item_align)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "out_items is not aligned to %u bytes", item_align);
-    const struct
-    {
-        const void* ptr;
-        size_t bytes;
-        const char* name;
-    } arrays[5] = {{out_segments, total * 4, "out_segments"},
-                   {out_ranks, total * 4, "out_ranks"},
-                   {out_items, total * item_bytes, "out_items"},
-                   {offsets, (num_segments + 1) * 4, "offsets"},
-                   {items, num_segments * item_bytes, "items"}};
-    for (int o = 0; o < 3; o++) // an output against every array behind it: the other outputs and the inputs
-        for (int i = o + 1; i < 5; i++)
-            if (arrays[o].ptr && arrays[i].ptr && overlaps(arrays[i].ptr, arrays[i].bytes, arrays[o].ptr, arrays[o].bytes))
-                return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", arrays[o].name, arrays[i].name);
+    GLU_TRY(check_aligned_4(offsets, "offsets"));
+    GLU_TRY(check_aligned_4(out_segments, "out_segments"));
+    GLU_TRY(check_aligned_4(out_ranks, "out_ranks"));
+    GLU_TRY(check_items_aligned(items, out_items, item_bytes, bytes_text(item_align(item_bytes))));
+    // an output against every array behind it: the other outputs and the inputs
+    GLU_TRY(check_disjoint({{out_segments, total * 4, "out_segments"}, {out_ranks, total * 4, "out_ranks"}, {out_items, total * item_bytes, "out_items"}},
+                           {{offsets, (num_segments + 1) * 4, "offsets"}, {items, num_segments * item_bytes, "items"}}, kOutputsBeforeInputs));
 
     if (!out_segments && !out_ranks && !out_items) // nothing asked for
     {
@@ -143,9 +114,9 @@ glu_status glu_expand_run_ptr(glu_expand expand, const uint32_t* offsets, size_t
 glu_status glu_expand_last(glu_expand expand, uint32_t* tiles, uint32_t* kernels)
 {
     GLU_TRY(enter());
-    if (!expand) return fail(GLU_ERROR_INVALID_ARGUMENT, "expand is NULL");
-    if (tiles) *tiles = expand->last.tiles;
-    if (kernels) *kernels = expand->last.kernels;
+    GLU_TRY(check_not_null(expand, "expand"));
+    store(tiles, expand->last.tiles);
+    store(kernels, expand->last.kernels);
     return GLU_OK;
 }
 

@@ -11,13 +11,6 @@ using namespace glu_hip::host;
 
 namespace
 {
-glu_status check_key_type(int key_type)
-{
-    return key_type >= (int) GLU_KEY_UINT32 && key_type <= (int) GLU_KEY_FLOAT64 ? GLU_OK
-                                                                                 : fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", key_type);
-}
-uint32_t key_bytes_of(int key_type) { return key_type >= (int) GLU_KEY_UINT64 ? 8u : 4u; }
-
 // what both entry points and the plan check of the counts: the key type, count, bins against the limit of the mode
 glu_status check_counts(size_t count, size_t bins, int key_type, int mode)
 {
@@ -40,13 +33,11 @@ glu_status check_arrays(const void* samples, size_t count, uint32_t kb, const vo
     if (count && !samples) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid samples buffer");
     if (!out_counts) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid out_counts buffer");
     if (with_edges && !edges) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid edges buffer");
-    if (count && (uintptr_t) samples % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "samples is not aligned to the sample size");
-    if ((uintptr_t) out_counts % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_counts is not aligned to 4 bytes");
-    if (with_edges && (uintptr_t) edges % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "edges is not aligned to the sample size");
-    if (count && overlaps(samples, count * kb, out_counts, bins * sizeof(uint32_t))) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_counts overlaps samples");
-    if (with_edges && overlaps(edges, (bins + 1) * kb, out_counts, bins * sizeof(uint32_t)))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "out_counts overlaps edges");
-    return GLU_OK;
+    if (count) GLU_TRY(check_aligned(samples, kb, "samples", "the sample size"));
+    GLU_TRY(check_aligned_4(out_counts, "out_counts"));
+    if (with_edges) GLU_TRY(check_aligned(edges, kb, "edges", "the sample size"));
+    return check_disjoint({{out_counts, bins * sizeof(uint32_t), "out_counts"}},
+                          {{samples, count * kb, "samples"}, {with_edges ? edges : nullptr, (bins + 1) * kb, "edges"}});
 }
 
 // the samples as the 16-byte packs from the boundary at or below them, in tiles of `tile` elements
@@ -129,37 +120,23 @@ glu_status glu_histogram_plan(size_t count, size_t bins, glu_key_type key_type, 
 {
     GLU_TRY(check_counts(count, bins, (int) key_type, mode));
     const HistPlan p = hist_plan(count, (uint32_t) bins, key_bytes_of((int) key_type), mode, false);
-    if (path) *path = p.path;
-    if (threads) *threads = p.threads;
-    if (tile) *tile = p.tile;
-    if (groups) *groups = p.groups;
-    if (kernels) *kernels = p.kernels;
-    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    store(path, p.path);
+    store(threads, p.threads);
+    store(tile, p.tile);
+    store(groups, p.groups);
+    store(kernels, p.kernels);
+    store(scratch_bytes, p.scratch_bytes);
     return GLU_OK;
 }
 
-glu_status glu_histogram_create(glu_histogram* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_histogram_s();
-    return GLU_OK;
-}
+glu_status glu_histogram_create(glu_histogram* out) { return create_object(out); }
 
-glu_status glu_histogram_destroy(glu_histogram histogram)
-{
-    GLU_TRY(enter());
-    if (!histogram) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    histogram->partial.release();
-    delete histogram;
-    return GLU_OK;
-}
+glu_status glu_histogram_destroy(glu_histogram histogram) { return destroy_object(histogram); }
 
 glu_status glu_histogram_prepare(glu_histogram histogram, size_t count, size_t bins)
 {
     GLU_TRY(enter());
-    if (!histogram) return fail(GLU_ERROR_INVALID_ARGUMENT, "histogram is NULL");
+    GLU_TRY(check_not_null(histogram, "histogram"));
     GLU_TRY(check_counts(count, bins, (int) GLU_KEY_UINT32, HIST_EVEN));
     return histogram->partial.reserve(hist_scratch_most(count, (uint32_t) bins));
 }
@@ -168,10 +145,10 @@ glu_status glu_histogram_run_even_ptr(glu_histogram histogram, const void* sampl
                                       const void* hi, size_t bins, uint32_t* out_counts, int accumulate, void* stream)
 {
     GLU_TRY(enter());
-    if (!histogram) return fail(GLU_ERROR_INVALID_ARGUMENT, "histogram is NULL");
+    GLU_TRY(check_not_null(histogram, "histogram"));
     GLU_TRY(check_counts(count, bins, (int) key_type, HIST_EVEN));
-    if (!lo) return fail(GLU_ERROR_INVALID_ARGUMENT, "lo is NULL");
-    if (!hi) return fail(GLU_ERROR_INVALID_ARGUMENT, "hi is NULL");
+    GLU_TRY(check_not_null(lo, "lo"));
+    GLU_TRY(check_not_null(hi, "hi"));
     GLU_TRY(check_arrays(samples, count, 4u * (key_type == GLU_KEY_FLOAT64 ? 2u : 1u), nullptr, false, bins, out_counts));
     const hipStream_t st = pick_stream(stream);
     const uint32_t nb = (uint32_t) bins;
@@ -203,7 +180,7 @@ glu_status glu_histogram_run_edges_ptr(glu_histogram histogram, const void* samp
                                        size_t bins, uint32_t* out_counts, int accumulate, void* stream)
 {
     GLU_TRY(enter());
-    if (!histogram) return fail(GLU_ERROR_INVALID_ARGUMENT, "histogram is NULL");
+    GLU_TRY(check_not_null(histogram, "histogram"));
     GLU_TRY(check_counts(count, bins, (int) key_type, HIST_EDGES));
     GLU_TRY(check_arrays(samples, count, key_bytes_of((int) key_type), edges, true, bins, out_counts));
     const hipStream_t st = pick_stream(stream);
@@ -223,10 +200,10 @@ glu_status glu_histogram_run_edges_ptr(glu_histogram histogram, const void* samp
 glu_status glu_histogram_last(glu_histogram histogram, uint32_t* path, uint32_t* groups, uint32_t* kernels)
 {
     GLU_TRY(enter());
-    if (!histogram) return fail(GLU_ERROR_INVALID_ARGUMENT, "histogram is NULL");
-    if (path) *path = histogram->last.path;
-    if (groups) *groups = histogram->last.groups;
-    if (kernels) *kernels = histogram->last.kernels;
+    GLU_TRY(check_not_null(histogram, "histogram"));
+    store(path, histogram->last.path);
+    store(groups, histogram->last.groups);
+    store(kernels, histogram->last.kernels);
     return GLU_OK;
 }
 

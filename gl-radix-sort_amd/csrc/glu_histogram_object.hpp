@@ -13,6 +13,7 @@ struct glu_histogram_s
     {
         uint32_t path = 0, groups = 0, kernels = 0;
     } last;
+    void release() { partial.release(); }
 };
 
 namespace glu_hip

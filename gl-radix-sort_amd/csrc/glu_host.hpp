@@ -19,6 +19,8 @@
 // The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
 // Key runs, select, sorted search, merge, histogram and expand share glu_tile_host.hpp on the host side; the first three and histogram share
 // tile_span.hpp (the tiles, the packs of an array at any alignment) on both sides.
+// The argument rules every unit checks by (key types, limits, overlap, alignment, items, handles, out-parameters) are glu_args.hpp's,
+// plain C++ that this header includes; the life of an operator object that owns only scratch is create_object / destroy_object below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,8 +30,7 @@
 #include <mutex>
 #include <string>
 
-#define GLU_HIP_BUILD 1
-#include "glu_hip.h"
+#include "glu_args.hpp"
 
 namespace glu_hip
 {
@@ -44,8 +45,6 @@ bool glu_verbose();
 // tuning lists of the placement search / scan / reduce, and the test hooks of glu_dist (fault injection, the RCCL test double).
 const char* glu_env(const char* name);
 
-glu_status fail(glu_status code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
 #define HIP_TRY(expr)                                                                                                  \
     do                                                                                                                 \
     {                                                                                                                  \
@@ -53,13 +52,6 @@ glu_status fail(glu_status code, const char* fmt, ...) __attribute__((format(pri
         if (e_ != hipSuccess)                                                                                          \
             return fail(e_ == hipErrorOutOfMemory ? GLU_ERROR_OUT_OF_MEMORY : GLU_ERROR_DEVICE, "%s failed: %s", #expr, \
                         hipGetErrorString(e_));                                                                        \
-    } while (0)
-
-#define GLU_TRY(expr)                                                                                                  \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        glu_status s_ = (expr);                                                                                        \
-        if (s_ != GLU_OK) return s_;                                                                                   \
     } while (0)
 
 // ------------------------------------------------------------------------------------------------------------
@@ -122,5 +114,41 @@ struct Scratch
         size = 0;
     }
 };
+
+// The life of an operator object T whose device memory is Scratch members: T::release() releases every one of them.
+// glu_*_create: `init` sets the new object up from the call's other arguments and may refuse them.
+template<typename T, typename Init>
+glu_status create_object(T** out, Init&& init)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(out, "out"));
+    T* object = new T();
+    const glu_status status = init(*object);
+    if (status != GLU_OK)
+    {
+        object->release();
+        delete object;
+        return status;
+    }
+    *out = object;
+    return GLU_OK;
+}
+template<typename T>
+glu_status create_object(T** out)
+{
+    return create_object(out, [](T&) { return GLU_OK; });
+}
+
+// glu_*_destroy: NULL is fine
+template<typename T>
+glu_status destroy_object(T* object)
+{
+    GLU_TRY(enter());
+    if (!object) return GLU_OK;
+    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
+    object->release();
+    delete object;
+    return GLU_OK;
+}
 } // namespace host
 } // namespace glu_hip

@@ -73,34 +73,20 @@ glu_status glu_key_runs_plan(size_t count, uint32_t key_bits, uint32_t* tile, ui
     GLU_TRY(check_key_bits(key_bits));
     GLU_TRY(check_count(count));
     const TilePlan p = tile_plan(count, key_bits / 8, kKeyRunsPacks);
-    if (tile) *tile = p.tile;
-    if (tiles) *tiles = p.tiles;
-    if (scan_rounds) *scan_rounds = p.scan_rounds;
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(scan_rounds, p.scan_rounds);
     return GLU_OK;
 }
 
-glu_status glu_key_runs_create(glu_key_runs* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_key_runs_s();
-    return GLU_OK;
-}
+glu_status glu_key_runs_create(glu_key_runs* out) { return create_object(out); }
 
-glu_status glu_key_runs_destroy(glu_key_runs runs)
-{
-    GLU_TRY(enter());
-    if (!runs) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    runs->tile_counts.release();
-    delete runs;
-    return GLU_OK;
-}
+glu_status glu_key_runs_destroy(glu_key_runs runs) { return destroy_object(runs); }
 
 glu_status glu_key_runs_prepare(glu_key_runs runs, size_t count, uint32_t key_bits)
 {
     GLU_TRY(enter());
-    if (!runs) return fail(GLU_ERROR_INVALID_ARGUMENT, "runs is NULL");
+    GLU_TRY(check_not_null(runs, "runs"));
     GLU_TRY(check_key_bits(key_bits));
     GLU_TRY(check_count(count));
     return runs->tile_counts.reserve(count, key_bits / 8, kKeyRunsPacks);
@@ -110,25 +96,24 @@ glu_status glu_key_runs_run_ptr(glu_key_runs runs, const void* keys, size_t coun
                                 uint32_t end_bit, void* unique_keys, uint32_t* offsets, size_t max_runs, uint32_t* num_runs, void* stream)
 {
     GLU_TRY(enter());
-    if (!runs) return fail(GLU_ERROR_INVALID_ARGUMENT, "runs is NULL");
+    GLU_TRY(check_not_null(runs, "runs"));
     GLU_TRY(check_key_bits(key_bits));
     GLU_TRY(check_count(count));
-    if (max_runs >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "max_runs must be below 2^32 (got %zu)", max_runs);
+    GLU_TRY(check_below_2_32(max_runs, "max_runs"));
     if (begin_bit > end_bit || end_bit > key_bits)
         return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid bit range [%u, %u) of %u-bit keys", begin_bit, end_bit, key_bits);
     if (count && !keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
     if (!offsets) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid offsets array");
     if (!num_runs) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid num_runs pointer");
     const size_t key_bytes = key_bits / 8;
-    if ((uintptr_t) keys % key_bytes) return fail(GLU_ERROR_INVALID_ARGUMENT, "keys is not aligned to the key size");
-    if ((uintptr_t) unique_keys % key_bytes) return fail(GLU_ERROR_INVALID_ARGUMENT, "unique_keys is not aligned to the key size");
-    if ((uintptr_t) offsets % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the offsets array is not aligned to its element size");
-    if ((uintptr_t) num_runs % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_runs is not aligned to 4 bytes");
-    if (overlaps(keys, count * key_bytes, offsets, (max_runs + 1) * sizeof(uint32_t)))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "the offsets array overlaps keys");
-    if (unique_keys && overlaps(keys, count * key_bytes, unique_keys, max_runs * key_bytes))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "unique_keys overlaps keys");
-    if (overlaps(keys, count * key_bytes, num_runs, sizeof(uint32_t))) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_runs overlaps keys");
+    GLU_TRY(check_aligned(keys, key_bytes, "keys", "the key size"));
+    GLU_TRY(check_aligned(unique_keys, key_bytes, "unique_keys", "the key size"));
+    GLU_TRY(check_aligned(offsets, sizeof(uint32_t), "the offsets array", "its element size"));
+    GLU_TRY(check_aligned_4(num_runs, "num_runs"));
+    // (the outputs are not held against each other)
+    GLU_TRY(check_disjoint({{offsets, (max_runs + 1) * sizeof(uint32_t), "the offsets array"}, {unique_keys, max_runs * key_bytes, "unique_keys"},
+                            {num_runs, sizeof(uint32_t), "num_runs"}},
+                           {{keys, count * key_bytes, "keys"}}));
     GLU_TRY(runs->tile_counts.reserve(count, key_bits / 8, kKeyRunsPacks));
     const Call c{runs, keys, count, begin_bit, end_bit, unique_keys, offsets, max_runs, num_runs, pick_stream(stream)};
     return key_bits == 64 ? run<uint64_t>(c) : run<uint32_t>(c);

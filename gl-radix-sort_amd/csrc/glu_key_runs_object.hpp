@@ -6,4 +6,5 @@
 struct glu_key_runs_s
 {
     glu_hip::host::TileCounts tile_counts; // heads per tile of the keys
+    void release() { tile_counts.release(); }
 };

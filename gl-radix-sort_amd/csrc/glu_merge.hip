@@ -11,23 +11,6 @@ using namespace glu_hip::host;
 
 namespace
 {
-glu_status check_key_type(int key_type)
-{
-    return key_type >= (int) GLU_KEY_UINT32 && key_type <= (int) GLU_KEY_FLOAT64 ? GLU_OK
-                                                                                 : fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", key_type);
-}
-uint32_t key_bytes_of(int key_type) { return key_type >= (int) GLU_KEY_UINT64 ? 8u : 4u; }
-uint32_t key_xf_of(int key_type)
-{
-    switch (key_type)
-    {
-    case GLU_KEY_INT32:
-    case GLU_KEY_INT64: return KEY_XF_SIGNED;
-    case GLU_KEY_FLOAT32:
-    case GLU_KEY_FLOAT64: return KEY_XF_FLOAT;
-    default: return KEY_XF_NONE;
-    }
-}
 // (each count first: their sum must not wrap)
 glu_status check_total(size_t a_count, size_t b_count)
 {
@@ -77,35 +60,21 @@ glu_status glu_merge_plan(size_t a_count, size_t b_count, glu_key_type key_type,
     GLU_TRY(check_key_type((int) key_type));
     GLU_TRY(check_total(a_count, b_count));
     const MergePlan p = merge_plan((uint64_t) a_count + b_count, key_bytes_of((int) key_type), with_vals != 0);
-    if (tile) *tile = p.tile;
-    if (tiles) *tiles = p.tiles;
-    if (kernels) *kernels = p.kernels;
-    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(kernels, p.kernels);
+    store(scratch_bytes, p.scratch_bytes);
     return GLU_OK;
 }
 
-glu_status glu_merge_create(glu_merge* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_merge_s();
-    return GLU_OK;
-}
+glu_status glu_merge_create(glu_merge* out) { return create_object(out); }
 
-glu_status glu_merge_destroy(glu_merge merge)
-{
-    GLU_TRY(enter());
-    if (!merge) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    merge->split.release();
-    delete merge;
-    return GLU_OK;
-}
+glu_status glu_merge_destroy(glu_merge merge) { return destroy_object(merge); }
 
 glu_status glu_merge_prepare(glu_merge merge, size_t total_count, glu_key_type key_type)
 {
     GLU_TRY(enter());
-    if (!merge) return fail(GLU_ERROR_INVALID_ARGUMENT, "merge is NULL");
+    GLU_TRY(check_not_null(merge, "merge"));
     GLU_TRY(check_key_type((int) key_type));
     GLU_TRY(check_total(total_count, 0));
     // (the tile is the same with and without values)
@@ -116,7 +85,7 @@ glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const uint32_t
                              const uint32_t* b_vals, size_t b_count, void* out_keys, uint32_t* out_vals, glu_key_type key_type, void* stream)
 {
     GLU_TRY(enter());
-    if (!merge) return fail(GLU_ERROR_INVALID_ARGUMENT, "merge is NULL");
+    GLU_TRY(check_not_null(merge, "merge"));
     GLU_TRY(check_key_type((int) key_type));
     GLU_TRY(check_total(a_count, b_count));
     const uint32_t kb = key_bytes_of((int) key_type);
@@ -131,24 +100,15 @@ glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const uint32_t
     const bool with_vals = out_vals != nullptr;
     if ((a_count && (a_vals != nullptr) != with_vals) || (b_count && (b_vals != nullptr) != with_vals))
         return fail(GLU_ERROR_INVALID_ARGUMENT, "a_vals, b_vals and out_vals must be all NULL (keys only) or all non-NULL");
-    if ((uintptr_t) a_keys % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "a_keys is not aligned to the key size");
-    if ((uintptr_t) b_keys % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "b_keys is not aligned to the key size");
-    if ((uintptr_t) out_keys % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_keys is not aligned to the key size");
-    if ((uintptr_t) a_vals % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "a_vals is not aligned to 4 bytes");
-    if ((uintptr_t) b_vals % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "b_vals is not aligned to 4 bytes");
-    if ((uintptr_t) out_vals % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_vals is not aligned to 4 bytes");
-    const struct
-    {
-        const void* ptr;
-        size_t bytes;
-        const char* name;
-    } inputs[4] = {{a_keys, a_count * kb, "a_keys"}, {b_keys, b_count * kb, "b_keys"}, {a_vals, a_count * 4, "a_vals"}, {b_vals, b_count * 4, "b_vals"}},
-      outputs[2] = {{out_keys, total * kb, "out_keys"}, {out_vals, total * 4, "out_vals"}};
-    for (const auto& o : outputs)
-        for (const auto& i : inputs)
-            if (o.ptr && i.ptr && overlaps(i.ptr, i.bytes, o.ptr, o.bytes))
-                return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", o.name, i.name);
-    if (out_vals && overlaps(out_keys, total * kb, out_vals, total * 4)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_vals overlaps out_keys");
+    GLU_TRY(check_aligned(a_keys, kb, "a_keys", "the key size"));
+    GLU_TRY(check_aligned(b_keys, kb, "b_keys", "the key size"));
+    GLU_TRY(check_aligned(out_keys, kb, "out_keys", "the key size"));
+    GLU_TRY(check_aligned_4(a_vals, "a_vals"));
+    GLU_TRY(check_aligned_4(b_vals, "b_vals"));
+    GLU_TRY(check_aligned_4(out_vals, "out_vals"));
+    GLU_TRY(check_disjoint({{out_keys, total * kb, "out_keys"}, {out_vals, total * 4, "out_vals"}},
+                           {{a_keys, a_count * kb, "a_keys"}, {b_keys, b_count * kb, "b_keys"}, {a_vals, a_count * 4, "a_vals"}, {b_vals, b_count * 4, "b_vals"}},
+                           kOutputsAfterInputs));
 
     const MergePlan p = merge_plan(total, kb, with_vals);
     merge->last = {p.tiles, p.kernels};
@@ -162,9 +122,9 @@ glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const uint32_t
 glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels)
 {
     GLU_TRY(enter());
-    if (!merge) return fail(GLU_ERROR_INVALID_ARGUMENT, "merge is NULL");
-    if (tiles) *tiles = merge->last.tiles;
-    if (kernels) *kernels = merge->last.kernels;
+    GLU_TRY(check_not_null(merge, "merge"));
+    store(tiles, merge->last.tiles);
+    store(kernels, merge->last.kernels);
     return GLU_OK;
 }
 

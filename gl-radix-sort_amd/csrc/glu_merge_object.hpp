@@ -13,6 +13,7 @@ struct glu_merge_s
     {
         uint32_t tiles = 0, kernels = 0;
     } last;
+    void release() { split.release(); }
 };
 
 namespace glu_hip

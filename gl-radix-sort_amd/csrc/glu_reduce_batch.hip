@@ -180,12 +180,10 @@ glu_status check_arrays(const glu_reduce_s* r, const void* data, const void* out
     const size_t align = std::min<size_t>(16, es);
     if (elements && !data) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data buffer");
     if (results && !out) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid output buffer");
-    if ((uintptr_t) data % align) return fail(GLU_ERROR_INVALID_ARGUMENT, "data is not aligned to its element size");
-    if ((uintptr_t) out % align) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is not aligned to its element size");
+    GLU_TRY(check_aligned(data, align, "data", "its element size"));
+    GLU_TRY(check_aligned(out, align, "out", "its element size"));
     if (elements > ((size_t) -1) / es) return fail(GLU_ERROR_INVALID_ARGUMENT, "the batch is larger than the address space");
-    const uintptr_t d0 = (uintptr_t) data, d1 = d0 + elements * es, o0 = (uintptr_t) out, o1 = o0 + results * es;
-    if (elements && results && d0 < o1 && o0 < d1) return fail(GLU_ERROR_INVALID_ARGUMENT, "out overlaps data");
-    return GLU_OK;
+    return check_disjoint({{out, results * es, "out"}}, {{data, elements * es, "data"}});
 }
 } // namespace
 
@@ -197,15 +195,15 @@ glu_status glu_reduce_plan_batch(size_t count, uint32_t elem_bytes, uint32_t* pa
         return fail(GLU_ERROR_INVALID_ARGUMENT, "elem_bytes must be 4, 8, 16 or 32 (got %u)", elem_bytes);
     uint32_t p, w;
     reduce_batch_plan(count, elem_bytes, p, w);
-    if (path) *path = p;
-    if (workgroups) *workgroups = w;
+    store(path, p);
+    store(workgroups, w);
     return GLU_OK;
 }
 
 glu_status glu_reduce_prepare_batch(glu_reduce reduce, size_t total, size_t num_segments)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     GLU_TRY(check_batch_total(total));
     GLU_TRY(check_batch_segments(num_segments));
     const size_t elem_bytes = data_type_size(reduce->type);
@@ -217,7 +215,7 @@ glu_status glu_reduce_prepare_batch(glu_reduce reduce, size_t total, size_t num_
 glu_status glu_reduce_run_batch_ptr(glu_reduce reduce, const void* data, void* out, size_t count, size_t num_partitions, void* stream)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     if (num_partitions >= ((size_t) 1 << 31)) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_partitions %zu is not below 2^31", num_partitions);
     if (count && num_partitions > ((size_t) -1) / count) return fail(GLU_ERROR_INVALID_ARGUMENT, "count * num_partitions overflows");
     GLU_TRY(check_arrays(reduce, data, out, count * num_partitions, num_partitions));
@@ -234,7 +232,7 @@ glu_status glu_reduce_run_batch_offsets_ptr(glu_reduce reduce, const void* data,
                                             size_t num_segments, void* stream)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     GLU_TRY(check_batch_total(total));
     GLU_TRY(check_batch_segments(num_segments));
     GLU_TRY(check_arrays(reduce, data, out, num_segments ? total : 0, num_segments));
@@ -251,7 +249,7 @@ glu_status glu_reduce_run_batch_offsets_ptr(glu_reduce reduce, const void* data,
 glu_status glu_reduce_read_batch(glu_reduce reduce, uint32_t* wave_segments, uint32_t* block_segments, uint32_t* long_segments)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     return reduce->last_batch.read(reduce->batch_lists, 3, wave_segments, block_segments, long_segments); // (the three short lists)
 }
 

@@ -13,6 +13,10 @@ struct glu_reduce_s
     glu_hip::host::Scratch batch_lists;
     glu_hip::host::Scratch batch_partials;
     glu_hip::host::LastBatch last_batch; // segments per class of the last batched call (glu_reduce_read_batch)
+    void release()
+    {
+        for (glu_hip::host::Scratch* s : {&partials, &batch_lists, &batch_partials}) s->release();
+    }
 };
 
 namespace glu_hip

@@ -105,15 +105,15 @@ glu_status glu_scan_plan_batch(size_t count, uint32_t elem_bytes, uint32_t* path
         return fail(GLU_ERROR_INVALID_ARGUMENT, "elem_bytes must be 4, 8, 16 or 32 (got %u)", elem_bytes);
     uint32_t p, w;
     scan_batch_plan(count, elem_bytes, p, w);
-    if (path) *path = p;
-    if (workgroups) *workgroups = w;
+    store(path, p);
+    store(workgroups, w);
     return GLU_OK;
 }
 
 glu_status glu_scan_prepare_batch(glu_scan scan, size_t total, size_t num_segments)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     GLU_TRY(check_batch_total(total));
     GLU_TRY(check_batch_segments(num_segments));
     const size_t elem_bytes = data_type_size(scan->type);
@@ -126,7 +126,7 @@ glu_status glu_scan_run_batch_offsets_ptr(glu_scan scan, void* data, size_t tota
                                           void* stream)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     GLU_TRY(check_batch_total(total));
     GLU_TRY(check_batch_segments(num_segments));
     if (num_segments == 0)
@@ -136,8 +136,7 @@ glu_status glu_scan_run_batch_offsets_ptr(glu_scan scan, void* data, size_t tota
     }
     if (total && !data) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data buffer");
     GLU_TRY(check_batch_offsets(offsets, num_segments));
-    if ((uintptr_t) data % std::min<size_t>(16, data_type_size(scan->type)))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "data is not aligned to its element size");
+    GLU_TRY(check_aligned(data, std::min<size_t>(16, data_type_size(scan->type)), "data", "its element size"));
     if (total == 0) // every segment is empty
     {
         scan->last_batch.reset();
@@ -150,7 +149,7 @@ glu_status glu_scan_run_batch_offsets_ptr(glu_scan scan, void* data, size_t tota
 glu_status glu_scan_read_batch(glu_scan scan, uint32_t* wave_segments, uint32_t* block_segments, uint32_t* long_segments)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     return scan->last_batch.read(scan->batch_lists, 3, wave_segments, block_segments, long_segments); // (the three short lists)
 }
 

@@ -19,4 +19,8 @@ struct glu_scan_s
     glu_hip::host::Scratch batch_lists;
     glu_hip::host::Scratch batch_partials;
     glu_hip::host::LastBatch last_batch; // segments per class of the last batched call (glu_scan_read_batch)
+    void release()
+    {
+        for (glu_hip::host::Scratch* s : {&sums, &chain, &ticket, &batch_lists, &batch_partials}) s->release();
+    }
 };

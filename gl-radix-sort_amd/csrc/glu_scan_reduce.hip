@@ -207,45 +207,35 @@ struct ReduceRunner
         }
     }
 };
+
+glu_status check_data_type(glu_data_type data_type)
+{
+    return (int) data_type >= 0 && data_type < GLU_DATA_TYPE_COUNT_ ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data type: %d", (int) data_type);
+}
 } // namespace
 
 extern "C" {
 
 glu_status glu_scan_create(glu_data_type data_type, glu_scan* out)
 {
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    if ((int) data_type < 0 || data_type >= GLU_DATA_TYPE_COUNT_)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data type: %d", (int) data_type);
-    glu_scan_s* s = new glu_scan_s();
-    s->type = data_type;
-    if (const char* e = glu_env("GLU_HIP_SCAN_CHAINED"))
-    {
-        s->chained = atoi(e) != 0;
-        if (atoi(e) == 2) s->chain_min_chunks = 2;
-    }
-    *out = s;
-    return GLU_OK;
+    return create_object(out, [&](glu_scan_s& s) -> glu_status {
+        GLU_TRY(check_data_type(data_type));
+        s.type = data_type;
+        if (const char* e = glu_env("GLU_HIP_SCAN_CHAINED"))
+        {
+            s.chained = atoi(e) != 0;
+            if (atoi(e) == 2) s.chain_min_chunks = 2;
+        }
+        return GLU_OK;
+    });
 }
 
-glu_status glu_scan_destroy(glu_scan scan)
-{
-    GLU_TRY(enter());
-    if (!scan) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    scan->sums.release();
-    scan->chain.release();
-    scan->ticket.release();
-    scan->batch_lists.release();
-    scan->batch_partials.release();
-    delete scan;
-    return GLU_OK;
-}
+glu_status glu_scan_destroy(glu_scan scan) { return destroy_object(scan); }
 
 glu_status glu_scan_prepare(glu_scan scan, size_t count, size_t num_partitions)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     if (count == 0 || num_partitions == 0) return GLU_OK;
     ScanRunner r{scan, nullptr, count, num_partitions, nullptr, true};
     return dispatch_type(scan->type, r);
@@ -254,12 +244,11 @@ glu_status glu_scan_prepare(glu_scan scan, size_t count, size_t num_partitions)
 glu_status glu_scan_run_ptr(glu_scan scan, void* data, size_t count, size_t num_partitions, void* stream)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     if (!data) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid buffer");
     if (count == 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "Count must be greater than zero");
     if (num_partitions < 1) return fail(GLU_ERROR_INVALID_ARGUMENT, "Num of partitions must be >= 1");
-    if (((uintptr_t) data % data_type_size(scan->type)) != 0)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "data is not aligned to its element size");
+    GLU_TRY(check_aligned(data, data_type_size(scan->type), "data", "its element size"));
     ScanRunner r{scan, data, count, num_partitions, pick_stream(stream), false};
     return dispatch_type(scan->type, r);
 }
@@ -267,7 +256,7 @@ glu_status glu_scan_run_ptr(glu_scan scan, void* data, size_t count, size_t num_
 glu_status glu_scan_run(glu_scan scan, glu_buffer buffer, size_t count, size_t num_partitions)
 {
     GLU_TRY(enter());
-    if (!scan) return fail(GLU_ERROR_INVALID_ARGUMENT, "scan is NULL");
+    GLU_TRY(check_not_null(scan, "scan"));
     Buffer b;
     GLU_TRY(lookup(buffer, b, "buffer"));                                                         // BlellochScan.hpp:132
     if (count == 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "Count must be greater than zero");    // :133
@@ -281,45 +270,25 @@ glu_status glu_scan_run(glu_scan scan, glu_buffer buffer, size_t count, size_t n
 
 glu_status glu_reduce_create(glu_data_type data_type, glu_reduce_operator op, glu_reduce* out)
 {
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    if ((int) data_type < 0 || data_type >= GLU_DATA_TYPE_COUNT_)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid data type: %d", (int) data_type);
-    if ((int) op < 0 || op >= GLU_REDUCE_COUNT_)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid reduction operator: %d", (int) op); // Reduce.hpp:94-97
-    glu_reduce_s* r = new glu_reduce_s();
-    r->type = data_type;
-    r->op = op;
-    glu_status st = r->partials.reserve((size_t) kReduceMaxBlocks * 32);
-    if (st != GLU_OK)
-    {
-        delete r;
-        return st;
-    }
-    *out = r;
-    return GLU_OK;
+    return create_object(out, [&](glu_reduce_s& r) -> glu_status {
+        GLU_TRY(check_data_type(data_type));
+        if ((int) op < 0 || op >= GLU_REDUCE_COUNT_)
+            return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid reduction operator: %d", (int) op); // Reduce.hpp:94-97
+        r.type = data_type;
+        r.op = op;
+        return r.partials.reserve((size_t) kReduceMaxBlocks * 32);
+    });
 }
 
-glu_status glu_reduce_destroy(glu_reduce reduce)
-{
-    GLU_TRY(enter());
-    if (!reduce) return GLU_OK;
-    (void) hipDeviceSynchronize();
-    reduce->partials.release();
-    reduce->batch_lists.release();
-    reduce->batch_partials.release();
-    delete reduce;
-    return GLU_OK;
-}
+glu_status glu_reduce_destroy(glu_reduce reduce) { return destroy_object(reduce); }
 
 glu_status glu_reduce_run_ptr(glu_reduce reduce, void* data, size_t count, void* stream)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     if (!data) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid buffer");
     if (count == 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "Count must be greater than zero");
-    if (((uintptr_t) data % std::min<size_t>(16, data_type_size(reduce->type))) != 0)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "data is not aligned to its element size");
+    GLU_TRY(check_aligned(data, std::min<size_t>(16, data_type_size(reduce->type)), "data", "its element size"));
     ReduceRunner r{reduce, data, count, pick_stream(stream)};
     return dispatch_type(reduce->type, r);
 }
@@ -327,7 +296,7 @@ glu_status glu_reduce_run_ptr(glu_reduce reduce, void* data, size_t count, void*
 glu_status glu_reduce_run(glu_reduce reduce, glu_buffer buffer, size_t count)
 {
     GLU_TRY(enter());
-    if (!reduce) return fail(GLU_ERROR_INVALID_ARGUMENT, "reduce is NULL");
+    GLU_TRY(check_not_null(reduce, "reduce"));
     Buffer b;
     GLU_TRY(lookup(buffer, b, "buffer"));                                                      // Reduce.hpp:113
     if (count == 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "Count must be greater than zero"); // Reduce.hpp:114

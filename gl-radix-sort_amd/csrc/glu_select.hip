@@ -103,34 +103,20 @@ glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint3
     GLU_TRY(check_count(count));
     const uint32_t sb = stencil_bytes(stencil_type);
     const TilePlan p = tile_plan(count, sb, select_packs(sb));
-    if (tile) *tile = p.tile;
-    if (tiles) *tiles = p.tiles;
-    if (scan_rounds) *scan_rounds = p.scan_rounds;
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(scan_rounds, p.scan_rounds);
     return GLU_OK;
 }
 
-glu_status glu_select_create(glu_select* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_select_s();
-    return GLU_OK;
-}
+glu_status glu_select_create(glu_select* out) { return create_object(out); }
 
-glu_status glu_select_destroy(glu_select select)
-{
-    GLU_TRY(enter());
-    if (!select) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    select->tile_counts.release();
-    delete select;
-    return GLU_OK;
-}
+glu_status glu_select_destroy(glu_select select) { return destroy_object(select); }
 
 glu_status glu_select_prepare(glu_select select, size_t count, int stencil_type)
 {
     GLU_TRY(enter());
-    if (!select) return fail(GLU_ERROR_INVALID_ARGUMENT, "select is NULL");
+    GLU_TRY(check_not_null(select, "select"));
     GLU_TRY(check_stencil_type(stencil_type));
     GLU_TRY(check_count(count));
     const uint32_t sb = stencil_bytes(stencil_type);
@@ -142,37 +128,25 @@ glu_status glu_select_run_ptr(glu_select select, const void* stencil, int stenci
                               uint32_t* num_selected, void* stream)
 {
     GLU_TRY(enter());
-    if (!select) return fail(GLU_ERROR_INVALID_ARGUMENT, "select is NULL");
+    GLU_TRY(check_not_null(select, "select"));
     GLU_TRY(check_stencil_type(stencil_type));
     if (op < 0 || op >= GLU_SELECT_OP_COUNT_) return fail(GLU_ERROR_INVALID_ARGUMENT, "op must be one of GLU_SELECT_EQ .. GLU_SELECT_GE (got %d)", op);
     GLU_TRY(check_count(count));
-    if (max_out >= ((size_t) 1 << 32)) return fail(GLU_ERROR_INVALID_ARGUMENT, "max_out must be below 2^32 (got %zu)", max_out);
+    GLU_TRY(check_below_2_32(max_out, "max_out"));
     if (count && !stencil) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid stencil buffer");
     if (!num_selected) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid num_selected pointer");
     if (!items != !out_items) return fail(GLU_ERROR_INVALID_ARGUMENT, "items and out_items must both be given or both be NULL");
-    if (items && item_bytes != 4 && item_bytes != 8 && item_bytes != 16 && item_bytes != 32)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "item_bytes must be 4, 8, 16 or 32 (got %u)", item_bytes);
-    const size_t sb = stencil_bytes(stencil_type);
-    const size_t ib = items ? item_bytes : 0, item_align = std::min<size_t>(ib, 16);
-    if ((uintptr_t) stencil % sb) return fail(GLU_ERROR_INVALID_ARGUMENT, "stencil is not aligned to its element size");
-    if (items && (uintptr_t) items % item_align) return fail(GLU_ERROR_INVALID_ARGUMENT, "items is not aligned to min(item_bytes, 16)");
-    if (items && (uintptr_t) out_items % item_align) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_items is not aligned to min(item_bytes, 16)");
-    if ((uintptr_t) out_indices % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_indices is not aligned to 4 bytes");
-    if ((uintptr_t) num_selected % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_selected is not aligned to 4 bytes");
-    // (no more than min(count, max_out) entries of an output array can be written)
+    if (items) GLU_TRY(check_item_bytes(item_bytes));
+    const size_t sb = stencil_bytes(stencil_type), ib = items ? item_bytes : 0;
+    GLU_TRY(check_aligned(stencil, sb, "stencil", "its element size"));
+    GLU_TRY(check_items_aligned(items, out_items, item_bytes, "min(item_bytes, 16)"));
+    GLU_TRY(check_aligned_4(out_indices, "out_indices"));
+    GLU_TRY(check_aligned_4(num_selected, "num_selected"));
+    // (no more than min(count, max_out) entries of an output array can be written; the outputs are not held against each other)
     const size_t written = std::min(count, max_out);
-    const struct
-    {
-        const void* ptr;
-        size_t bytes;
-        const char* name;
-    } inputs[2] = {{stencil, count * sb, "stencil"}, {items, count * ib, "items"}},
-      outputs[3] = {{out_items, written * ib, "out_items"}, {out_indices, out_indices ? written * sizeof(uint32_t) : 0, "out_indices"},
-                    {num_selected, sizeof(uint32_t), "num_selected"}};
-    for (const auto& o : outputs)
-        for (const auto& i : inputs)
-            if (o.ptr && i.ptr && overlaps(i.ptr, i.bytes, o.ptr, o.bytes))
-                return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", o.name, i.name);
+    GLU_TRY(check_disjoint({{out_items, written * ib, "out_items"}, {out_indices, written * sizeof(uint32_t), "out_indices"},
+                            {num_selected, sizeof(uint32_t), "num_selected"}},
+                           {{stencil, count * sb, "stencil"}, {items, count * ib, "items"}}));
     GLU_TRY(select->tile_counts.reserve(count, (uint32_t) sb, select_packs((uint32_t) sb)));
     const Call c{select, stencil, op, threshold, count, items, item_bytes, out_items, out_indices, max_out, num_selected, pick_stream(stream)};
     switch (stencil_type)

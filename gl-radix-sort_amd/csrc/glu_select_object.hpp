@@ -6,4 +6,5 @@
 struct glu_select_s
 {
     glu_hip::host::TileCounts tile_counts; // selected elements per tile of the stencil
+    void release() { tile_counts.release(); }
 };

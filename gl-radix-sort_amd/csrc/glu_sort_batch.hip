@@ -173,28 +173,15 @@ glu_status run_equal(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
     return launch_block<KeyT, VALS>(keys, vals, a, geo, stream);
 }
 
-inline uint32_t transform_of(glu_key_type t)
-{
-    switch (t)
-    {
-    case GLU_KEY_INT32:
-    case GLU_KEY_INT64: return KEY_XF_SIGNED;
-    case GLU_KEY_FLOAT32:
-    case GLU_KEY_FLOAT64: return KEY_XF_FLOAT;
-    default: return KEY_XF_NONE;
-    }
-}
-inline size_t key_bytes_of(glu_key_type t) { return (int) t >= (int) GLU_KEY_UINT64 ? 8 : 4; }
+static_assert(kKeyXfNone == KEY_XF_NONE && kKeyXfSigned == KEY_XF_SIGNED && kKeyXfFloat == KEY_XF_FLOAT, "key_xf_of() speaks the kernels' KEY_XF_*");
 
 glu_status check_arrays(const void* keys, const uint32_t* vals, size_t elements, glu_key_type key_type)
 {
-    if ((int) key_type < (int) GLU_KEY_UINT32 || (int) key_type > (int) GLU_KEY_FLOAT64)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", (int) key_type);
+    GLU_TRY(check_key_type(key_type));
     GLU_TRY(check_batch_total(elements));
     if (elements && !keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    if ((uintptr_t) keys % key_bytes_of(key_type)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the key array is not aligned to its element size");
-    if ((uintptr_t) vals % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "the value array is not aligned to its element size");
-    return GLU_OK;
+    GLU_TRY(check_aligned(keys, key_bytes_of(key_type), "the key array", "its element size"));
+    return check_aligned(vals, sizeof(uint32_t), "the value array", "its element size");
 }
 } // namespace
 
@@ -207,15 +194,15 @@ glu_status glu_radix_sort_plan_batch(size_t count, uint32_t key_bytes, int with_
     uint32_t p, t;
     int geo;
     plan_equal(count, key_bytes, p, t, geo);
-    if (path) *path = p;
-    if (tile) *tile = t;
+    store(path, p);
+    store(tile, t);
     return GLU_OK;
 }
 
 glu_status glu_radix_sort_prepare_batch(glu_radix_sort sort, size_t total, size_t num_segments, size_t key_bytes, int with_vals)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (key_bytes != 4 && key_bytes != 8) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bytes must be 4 or 8 (got %zu)", key_bytes);
     GLU_TRY(check_batch_total(total));
     GLU_TRY(check_batch_segments(num_segments));
@@ -231,7 +218,7 @@ glu_status glu_radix_sort_run_batch_ptr(glu_radix_sort sort, void* keys, uint32_
                                         glu_key_type key_type, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (count && num_partitions > ((size_t) -1) / count) return fail(GLU_ERROR_INVALID_ARGUMENT, "count * num_partitions overflows");
     GLU_TRY(check_arrays(keys, vals, count * num_partitions, key_type));
     GLU_TRY(check_batch_segments(num_partitions));
@@ -251,7 +238,7 @@ glu_status glu_radix_sort_run_batch_ptr(glu_radix_sort sort, void* keys, uint32_
             status = sort_typed_one_queue(sort, (char*) keys + p * count * key_bytes, vals ? vals + p * count : nullptr, count, key_type, st);
         return status;
     }
-    const uint32_t xf = transform_of(key_type);
+    const uint32_t xf = key_xf_of(key_type);
     if (key_bytes == 4)
         return vals ? run_equal<uint32_t, true>(sort, (uint32_t*) keys, vals, count, num_partitions, path, geo, xf, st)
                     : run_equal<uint32_t, false>(sort, (uint32_t*) keys, nullptr, count, num_partitions, path, geo, xf, st);
@@ -263,14 +250,14 @@ glu_status glu_radix_sort_run_batch_offsets_ptr(glu_radix_sort sort, void* keys,
                                                 size_t num_segments, glu_key_type key_type, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     GLU_TRY(check_arrays(keys, vals, total, key_type));
     GLU_TRY(check_batch_segments(num_segments));
     GLU_TRY(check_batch_offsets(offsets, num_segments));
     sort->last_batch.reset();
     if (num_segments == 0 || total < 2) return GLU_OK; // (no segment can hold two elements)
     hipStream_t st = pick_stream(stream);
-    const uint32_t xf = transform_of(key_type);
+    const uint32_t xf = key_xf_of(key_type);
     if (key_bytes_of(key_type) == 4)
         return vals ? run_offsets<uint32_t, true>(sort, (uint32_t*) keys, vals, total, offsets, num_segments, xf, st)
                     : run_offsets<uint32_t, false>(sort, (uint32_t*) keys, nullptr, total, offsets, num_segments, xf, st);
@@ -281,7 +268,7 @@ glu_status glu_radix_sort_run_batch_offsets_ptr(glu_radix_sort sort, void* keys,
 glu_status glu_radix_sort_read_batch(glu_radix_sort sort, uint32_t* wave_segments, uint32_t* block_segments, uint32_t* long_segments)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     return sort->last_batch.read(sort->batch_lists, 1, wave_segments, block_segments, long_segments); // (list 0: the wave class)
 }
 

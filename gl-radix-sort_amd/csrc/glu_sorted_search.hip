@@ -17,23 +17,6 @@ static_assert(kSearchLevelsMax == kSearchMaxLevels, "the host's level rule fills
 
 namespace
 {
-glu_status check_key_type(int key_type)
-{
-    return key_type >= (int) GLU_KEY_UINT32 && key_type <= (int) GLU_KEY_FLOAT64 ? GLU_OK
-                                                                                 : fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", key_type);
-}
-uint32_t key_bytes_of(int key_type) { return key_type >= (int) GLU_KEY_UINT64 ? 8u : 4u; }
-uint32_t key_xf_of(int key_type)
-{
-    switch (key_type)
-    {
-    case GLU_KEY_INT32:
-    case GLU_KEY_INT64: return KEY_XF_SIGNED;
-    case GLU_KEY_FLOAT32:
-    case GLU_KEY_FLOAT64: return KEY_XF_FLOAT;
-    default: return KEY_XF_NONE;
-    }
-}
 glu_status check_hay_count(size_t n) { return check_tile_count(n, "sorted search takes a hay_count below 2^32"); }
 glu_status check_needle_count(size_t n) { return check_tile_count(n, "sorted search takes a needle_count below 2^32"); }
 
@@ -145,11 +128,11 @@ void remember(glu_sorted_search_s* s, const void* hay, size_t hay_count, int key
 // what index_ptr and run_ptr check of a haystack
 glu_status check_hay(glu_sorted_search_s* s, const void* hay, size_t hay_count, int key_type)
 {
-    if (!s) return fail(GLU_ERROR_INVALID_ARGUMENT, "search is NULL");
+    GLU_TRY(check_not_null(s, "search"));
     GLU_TRY(check_key_type(key_type));
     GLU_TRY(check_hay_count(hay_count));
     if (hay_count && !hay) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid hay buffer");
-    if ((uintptr_t) hay % key_bytes_of(key_type)) return fail(GLU_ERROR_INVALID_ARGUMENT, "hay is not aligned to the key size");
+    GLU_TRY(check_aligned(hay, key_bytes_of(key_type), "hay", "the key size"));
     return check_top_entries(s->top_entries, key_bytes_of(key_type));
 }
 } // namespace
@@ -165,35 +148,21 @@ glu_status glu_sorted_search_plan(size_t hay_count, size_t needle_count, glu_key
     const uint32_t kb = key_bytes_of((int) key_type);
     GLU_TRY(check_top_entries(top_entries, kb));
     const SearchPlan p = search_plan(hay_count, kb, top_entries_of(top_entries, kb));
-    if (path) *path = (uint32_t) pick_path(GLU_SEARCH_PATH_AUTO, p, hay_count, needle_count);
-    if (levels) *levels = p.levels;
-    if (fanout) *fanout = p.fanout;
-    if (index_bytes) *index_bytes = p.index_bytes;
+    store(path, pick_path(GLU_SEARCH_PATH_AUTO, p, hay_count, needle_count));
+    store(levels, p.levels);
+    store(fanout, p.fanout);
+    store(index_bytes, p.index_bytes);
     return GLU_OK;
 }
 
-glu_status glu_sorted_search_create(glu_sorted_search* out)
-{
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    *out = new glu_sorted_search_s();
-    return GLU_OK;
-}
+glu_status glu_sorted_search_create(glu_sorted_search* out) { return create_object(out); }
 
-glu_status glu_sorted_search_destroy(glu_sorted_search search)
-{
-    GLU_TRY(enter());
-    if (!search) return GLU_OK;
-    (void) hipDeviceSynchronize(); // (a caller stream may still run its kernels)
-    search->index.release();
-    delete search;
-    return GLU_OK;
-}
+glu_status glu_sorted_search_destroy(glu_sorted_search search) { return destroy_object(search); }
 
 glu_status glu_sorted_search_prepare(glu_sorted_search search, size_t hay_count, glu_key_type key_type)
 {
     GLU_TRY(enter());
-    if (!search) return fail(GLU_ERROR_INVALID_ARGUMENT, "search is NULL");
+    GLU_TRY(check_not_null(search, "search"));
     GLU_TRY(check_key_type((int) key_type));
     GLU_TRY(check_hay_count(hay_count));
     const uint32_t kb = key_bytes_of((int) key_type);
@@ -204,8 +173,8 @@ glu_status glu_sorted_search_prepare(glu_sorted_search search, size_t hay_count,
 glu_status glu_sorted_search_set_option(glu_sorted_search search, const char* name, long long value)
 {
     GLU_TRY(enter());
-    if (!search) return fail(GLU_ERROR_INVALID_ARGUMENT, "search is NULL");
-    if (!name) return fail(GLU_ERROR_INVALID_ARGUMENT, "name is NULL");
+    GLU_TRY(check_not_null(search, "search"));
+    GLU_TRY(check_not_null(name, "name"));
     if (!strcmp(name, "PATH"))
     {
         if (value < GLU_SEARCH_PATH_AUTO || value > GLU_SEARCH_PATH_INDEXED)
@@ -251,23 +220,12 @@ glu_status glu_sorted_search_run_ptr(glu_sorted_search search, const void* hay, 
     const uint32_t kb = key_bytes_of((int) key_type), top = top_entries_of(search->top_entries, kb);
     if (needle_count && !needles) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid needles buffer");
     if (!out_lower && !out_upper) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_lower and out_upper are both NULL");
-    if ((uintptr_t) needles % kb) return fail(GLU_ERROR_INVALID_ARGUMENT, "needles is not aligned to the key size");
-    if ((uintptr_t) out_lower % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_lower is not aligned to 4 bytes");
-    if ((uintptr_t) out_upper % sizeof(uint32_t)) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_upper is not aligned to 4 bytes");
+    GLU_TRY(check_aligned(needles, kb, "needles", "the key size"));
+    GLU_TRY(check_aligned_4(out_lower, "out_lower"));
+    GLU_TRY(check_aligned_4(out_upper, "out_upper"));
     const size_t out_bytes = needle_count * sizeof(uint32_t);
-    const struct
-    {
-        const void* ptr;
-        size_t bytes;
-        const char* name;
-    } inputs[2] = {{hay, hay_count * kb, "hay"}, {needles, needle_count * kb, "needles"}},
-      outputs[2] = {{out_lower, out_bytes, "out_lower"}, {out_upper, out_bytes, "out_upper"}};
-    for (const auto& o : outputs)
-        for (const auto& i : inputs)
-            if (o.ptr && i.ptr && overlaps(i.ptr, i.bytes, o.ptr, o.bytes))
-                return fail(GLU_ERROR_INVALID_ARGUMENT, "%s overlaps %s", o.name, i.name);
-    if (out_lower && out_upper && overlaps(out_lower, out_bytes, out_upper, out_bytes))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "out_upper overlaps out_lower");
+    GLU_TRY(check_disjoint({{out_lower, out_bytes, "out_lower"}, {out_upper, out_bytes, "out_upper"}},
+                           {{hay, hay_count * kb, "hay"}, {needles, needle_count * kb, "needles"}}, kOutputsAfterInputs));
 
     const SearchPlan p = search_plan(hay_count, kb, top);
     bool indexed;
@@ -302,10 +260,10 @@ glu_status glu_sorted_search_run_ptr(glu_sorted_search search, const void* hay, 
 glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* path, uint32_t* levels, uint32_t* kernels)
 {
     GLU_TRY(enter());
-    if (!search) return fail(GLU_ERROR_INVALID_ARGUMENT, "search is NULL");
-    if (path) *path = search->last.path;
-    if (levels) *levels = search->last.levels;
-    if (kernels) *kernels = search->last.kernels;
+    GLU_TRY(check_not_null(search, "search"));
+    store(path, search->last.path);
+    store(levels, search->last.levels);
+    store(kernels, search->last.kernels);
     return GLU_OK;
 }
 

@@ -23,6 +23,7 @@ struct glu_sorted_search_s
     {
         uint32_t path = 0, levels = 0, kernels = 0;
     } last;
+    void release() { index.release(); }
 };
 
 namespace glu_hip

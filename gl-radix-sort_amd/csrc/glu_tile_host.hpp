@@ -1,5 +1,5 @@
-// glu_tile_host.hpp -- what glu_key_runs.hip and glu_select.hip share on the host side: the limit of a call, the overlap test of
-// two arrays, the tile counts an operator object owns, the grid of the streaming kernels and the launch of the count scan.
+// glu_tile_host.hpp -- what glu_key_runs.hip and glu_select.hip share on the host side: the tile counts an operator object owns,
+// the grid of the streaming kernels and the launch of the count scan.  (The limit of a call and the overlap test: glu_args.hpp.)
 #pragma once
 
 #include <algorithm>
@@ -11,18 +11,6 @@ namespace glu_hip
 {
 namespace host
 {
-// `what`: the operator's own sentence, e.g. "select takes a count below 2^32"
-inline glu_status check_tile_count(size_t count, const char* what)
-{
-    return count < ((size_t) 1 << 32) ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "%s (got %zu)", what, count);
-}
-
-inline bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t) a, b0 = (uintptr_t) b;
-    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // Flags per tile of an array, scanned in place by every call: 4 bytes per tile.  What glu_key_runs_s and glu_select_s are.
 struct TileCounts : Scratch
 {

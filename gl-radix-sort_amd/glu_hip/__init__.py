@@ -394,14 +394,37 @@ def _read_batch(fn, handle):
     return {"wave": a.value, "block": b.value, "long": c.value}
 
 
-class RadixSort:
+class _Handle:
+    """An object of the C ABI behind a handle: _CREATE(*arguments, &handle) makes it, _DESTROY(handle) ends it, once."""
+
+    _CREATE = _DESTROY = None
+    _borrowed = False  # the handle belongs to another object (Dist.sorter): never destroyed from here
+
+    def _create(self, *arguments):
+        self._h = _vp()
+        check(getattr(lib(), self._CREATE)(*arguments, ctypes.byref(self._h)))
+
+    def destroy(self):
+        if self._h and _lib is not None and not self._borrowed:
+            getattr(_lib, self._DESTROY)(self._h)
+        self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class RadixSort(_Handle):
     """glu::RadixSort (reference glu/RadixSort.hpp:186-354) over the C ABI."""
+
+    _CREATE, _DESTROY = "glu_radix_sort_create", "glu_radix_sort_destroy"
 
     def __init__(self, digit_bits=None, options=None):
         """options: {name: integer} switches for tests / tuning (glu_radix_sort_set_option; names as in the environment, with or
         without the GLU_HIP_ prefix) -- set on THIS object, the process environment is not touched."""
-        self._h = _vp()
-        check(lib().glu_radix_sort_create(ctypes.byref(self._h)))
+        self._create()
         if digit_bits is not None:
             check(lib().glu_radix_sort_set_digit_bits(self._h, digit_bits))
         for name, value in (options or {}).items():
@@ -552,26 +575,16 @@ class RadixSort:
         check(lib().glu_radix_sort_partition_ptr(self._h, _vp(src_keys), _vp(src_vals), _vp(dst_keys), _vp(dst_vals),
                                                  count, shift, bits, _vp(histogram_ptr), _vp(stream)))
 
-    def destroy(self):
-        if self._h and _lib is not None and not getattr(self, "_borrowed", False):
-            _lib.glu_radix_sort_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class KeyRuns:
+class KeyRuns(_Handle):
     """glu::KeyRuns (not in the reference) over the C ABI: the runs of equal keys as offsets for the batched calls."""
+
+    _CREATE, _DESTROY = "glu_key_runs_create", "glu_key_runs_destroy"
 
     MAX_COMPOSED_RUNS = 1 << 24  # the limit of the batched calls, which run_by_key_ptr of Reduce and BlellochScan go through
 
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_key_runs_create(ctypes.byref(self._h)))
+        self._create()
 
     def prepare(self, count, key_bits=32):
         """Scratch for up to `count` keys: after it run_ptr allocates nothing (capturable) (glu_key_runs_prepare)."""
@@ -585,27 +598,17 @@ class KeyRuns:
         check(lib().glu_key_runs_run_ptr(self._h, _vp(keys_ptr), count, key_bits, begin_bit, key_bits if end_bit is None else end_bit,
                                          _vp(unique_keys_ptr), _vp(offsets_ptr), max_runs, _vp(num_runs_ptr), _vp(stream)))
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_key_runs_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Select:
+class Select(_Handle):
     """glu::Select (not in the reference) over the C ABI: stable stream compaction by a stencil and a comparison."""
+
+    _CREATE, _DESTROY = "glu_select_create", "glu_select_destroy"
 
     _THRESHOLD_TYPES = {SelectStencil_Float: ctypes.c_float, SelectStencil_Double: ctypes.c_double, SelectStencil_Int: ctypes.c_int32,
                         SelectStencil_Uint: ctypes.c_uint32, SelectStencil_Byte: ctypes.c_uint8}
 
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_select_create(ctypes.byref(self._h)))
+        self._create()
 
     def prepare(self, count, stencil_type=SelectStencil_Uint):
         """Scratch for up to `count` elements: after it run_ptr allocates nothing (capturable) (glu_select_prepare)."""
@@ -631,26 +634,16 @@ class Select:
                                        _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr), max_out, _vp(num_selected_ptr),
                                        _vp(stream)))
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_select_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class SortedSearch:
+class SortedSearch(_Handle):
     """glu::SortedSearch (not in the reference) over the C ABI: lower and upper bounds of many needles in a sorted haystack."""
+
+    _CREATE, _DESTROY = "glu_sorted_search_create", "glu_sorted_search_destroy"
 
     NEEDLE_PACKS = 2  # 16-byte packs of needles per thread and tile (sorted_search_kernels.hpp: kSearchPacks)
 
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_sorted_search_create(ctypes.byref(self._h)))
+        self._create()
 
     @classmethod
     def needle_tile(cls, key_type="uint32"):
@@ -685,24 +678,14 @@ class SortedSearch:
         check(lib().glu_sorted_search_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_sorted_search_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Merge:
+class Merge(_Handle):
     """glu::Merge (not in the reference) over the C ABI: two sorted arrays of keys, with or without uint32 values, into one, stable."""
 
+    _CREATE, _DESTROY = "glu_merge_create", "glu_merge_destroy"
+
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_merge_create(ctypes.byref(self._h)))
+        self._create()
 
     def prepare(self, total_count, key_type="uint32"):
         """Scratch for calls of up to `total_count` = a_count + b_count keys: they allocate nothing (capturable) (glu_merge_prepare)."""
@@ -721,28 +704,18 @@ class Merge:
         check(lib().glu_merge_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_merge_destroy(self._h)
-        self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 _HISTOGRAM_BOUNDS = {"uint32": ctypes.c_uint32, "int32": ctypes.c_int32, "float32": ctypes.c_float, "float64": ctypes.c_double,
                      "uint64": ctypes.c_uint64, "int64": ctypes.c_int64}
 
 
-class Histogram:
+class Histogram(_Handle):
     """glu::Histogram (not in the reference) over the C ABI: uint32 counts of the samples per bin, over even bins or sorted edges."""
 
+    _CREATE, _DESTROY = "glu_histogram_create", "glu_histogram_destroy"
+
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_histogram_create(ctypes.byref(self._h)))
+        self._create()
 
     def prepare(self, count, bins):
         """Scratch for calls of up to `count` samples and `bins` bins: they allocate nothing (capturable) (glu_histogram_prepare)."""
@@ -777,25 +750,15 @@ class Histogram:
         check(lib().glu_histogram_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_histogram_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Expand:
+class Expand(_Handle):
     """glu::Expand (not in the reference) over the C ABI: for every element the segment that holds it, its rank inside the segment
     and the segment's item, from the offsets of the batched family.  The inverse of KeyRuns; numpy.repeat on the device."""
 
+    _CREATE, _DESTROY = "glu_expand_create", "glu_expand_destroy"
+
     def __init__(self):
-        self._h = _vp()
-        check(lib().glu_expand_create(ctypes.byref(self._h)))
+        self._create()
 
     def prepare(self, total, num_segments):
         """Scratch for calls of up to `total` elements and `num_segments` segments: they allocate nothing (capturable)
@@ -816,29 +779,19 @@ class Expand:
         check(lib().glu_expand_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_expand_destroy(self._h)
-        self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
 
 def _check_composed_runs(max_runs):
     if max_runs > KeyRuns.MAX_COMPOSED_RUNS:
         raise GluError(GLU_ERROR_INVALID_ARGUMENT, "max_runs %d exceeds 2^24" % max_runs)
 
 
-class BlellochScan:
+class BlellochScan(_Handle):
     """glu::BlellochScan (reference glu/BlellochScan.hpp:80-191) over the C ABI."""
 
+    _CREATE, _DESTROY = "glu_scan_create", "glu_scan_destroy"
+
     def __init__(self, data_type):
-        self._h = _vp()
-        check(lib().glu_scan_create(data_type, ctypes.byref(self._h)))
+        self._create(data_type)
 
     def __call__(self, buffer, count, num_partitions=1):
         b = buffer.handle() if isinstance(buffer, ShaderStorageBuffer) else buffer
@@ -873,24 +826,14 @@ class BlellochScan:
         """{wave, block, long}: segments each path of the last batched call took (glu_scan_read_batch); synchronise first."""
         return _read_batch(lib().glu_scan_read_batch, self._h)
 
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_scan_destroy(self._h)
-        self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Reduce:
+class Reduce(_Handle):
     """glu::Reduce (reference glu/Reduce.hpp:51-136) over the C ABI."""
 
+    _CREATE, _DESTROY = "glu_reduce_create", "glu_reduce_destroy"
+
     def __init__(self, data_type, operator_):
-        self._h = _vp()
-        check(lib().glu_reduce_create(data_type, operator_, ctypes.byref(self._h)))
+        self._create(data_type, operator_)
 
     def __call__(self, buffer, count):
         b = buffer.handle() if isinstance(buffer, ShaderStorageBuffer) else buffer
@@ -926,17 +869,6 @@ class Reduce:
     def read_batch(self):
         """{wave, block, long}: segments each path of the last batched call took (glu_reduce_read_batch); synchronise first."""
         return _read_batch(lib().glu_reduce_read_batch, self._h)
-
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_reduce_destroy(self._h)
-        self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def measure_elapsed_time(callback):
@@ -1005,12 +937,13 @@ def dist_plan_groups(all_hist, world_size, owner, rounds):
     return [list(cut[q * (rounds + 1):(q + 1) * (rounds + 1)]) for q in range(world_size)]
 
 
-class Dist:
+class Dist(_Handle):
     """glu_dist over the C ABI: the sharded sort of one rank (RCCL communicator + local sorter inside the library)."""
 
+    _CREATE, _DESTROY = "glu_dist_create", "glu_dist_destroy"
+
     def __init__(self, unique_id, world_size, rank):
-        self._h = _vp()
-        check(lib().glu_dist_create(unique_id, len(unique_id), world_size, rank, ctypes.byref(self._h)))
+        self._create(unique_id, len(unique_id), world_size, rank)
         self.world_size, self.rank = world_size, rank
 
     def prepare(self, local_count, recv_capacity=0):
@@ -1074,14 +1007,3 @@ class Dist:
         check(lib().glu_dist_phase_times(self._h, ms, ctypes.byref(n)))
         names = ("partition", "histogram_exchange_and_plan", "all_to_all", "local_sort")
         return {"sorts": int(n.value), **{k: float(ms[i]) for i, k in enumerate(names)}}
-
-    def destroy(self):
-        if self._h and _lib is not None:
-            _lib.glu_dist_destroy(self._h)
-        self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass

@@ -154,6 +154,28 @@ def test_cpp_api_exit_code_convention_without_gpu(built):
     assert "no CPU fallback" in p.stderr
 
 
+def test_one_make_in_tests_cpp_builds_every_api_test(built):
+    """tests/cpp/Makefile finds its programs itself: from its default goal it links every test_*_api.cpp on disk, bench_ladder and
+    the RCCL test double; build() runs it once, without -f."""
+    import inspect
+
+    import __graft_entry__ as entry
+
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    out = subprocess.run(["make", "-C", cpp, "--dry-run", "--always-make"], capture_output=True, text=True, check=True).stdout
+    links = [ln for ln in out.splitlines() if " -o bin/" in ln]
+    sources = sorted(f for f in os.listdir(cpp) if re.fullmatch(r"test_\w+_api\.cpp", f))
+    assert len(sources) >= 13
+    for src in sources + ["bench_ladder.cpp"]:
+        exe = "bin/" + src[:-len(".cpp")]
+        assert [ln for ln in links if "-o %s %s " % (exe, src) in ln and "-lglu_hip" in ln], src
+    assert [ln for ln in links if "-o bin/libmock_rccl.so mock_rccl.cpp" in ln and "-shared" in ln]
+    assert len(links) == len(sources) + 2
+    build = inspect.getsource(entry.build)
+    makes = [ln for ln in build.splitlines() if '_run(["make"' in ln and '"tests", "cpp"' in ln]
+    assert len(makes) == 1 and '"-f"' not in build and ".mk" not in build, makes
+
+
 def test_standalone_dist_headers_are_current_and_compile(tmp_path):
     """dist/{RadixSort,BlellochScan,Reduce}.hpp (the reference ships the same three, built by its generate.py) are what
     tools/make_dist.py produces from the current headers, and one translation unit can include all three."""

@@ -162,10 +162,6 @@ def test_the_standalone_header_is_generated_and_compiles(tmp_path):
 def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "Makefile")).read()
     assert "glu_expand" in mk and "expand_kernels.hpp" in mk and "expand_path.hpp" in mk and "glu_expand_object.hpp" in mk
-    inc = open(os.path.join(ROOT, "tests", "cpp", "expand.mk")).read()
-    assert "include histogram.mk" in inc and "test_expand_api" in inc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"expand.mk"' in entry
 
 
 def test_the_expand_kernels_are_built_without_scratch(built):

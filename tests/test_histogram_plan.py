@@ -190,10 +190,6 @@ def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     for name in ("glu_histogram", "histogram_kernels.hpp", "histogram_bins.hpp", "glu_histogram_object.hpp"):
         assert name in mk, name
-    inc = open(os.path.join(ROOT, "tests", "cpp", "histogram.mk")).read()
-    assert "include merge.mk" in inc and "test_histogram_api" in inc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"-f", "histogram.mk"' in entry
     assert "glu_histogram.hip" in open(os.path.join(CSRC, "glu_host.hpp")).read()
 
 

@@ -156,10 +156,6 @@ def test_the_standalone_header_is_generated_and_compiles(tmp_path):
 def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "Makefile")).read()
     assert "glu_merge" in mk and "merge_kernels.hpp" in mk and "merge_path.hpp" in mk and "glu_merge_object.hpp" in mk
-    inc = open(os.path.join(ROOT, "tests", "cpp", "merge.mk")).read()
-    assert "include sorted_search.mk" in inc and "test_merge_api" in inc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"merge.mk"' in entry
 
 
 def test_the_merge_kernels_are_built_for_both_key_widths_without_scratch(built):

@@ -124,5 +124,3 @@ def test_the_cpp_wrappers_instantiate(tmp_path):
 def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "Makefile")).read()
     assert "glu_reduce_batch" in mk and "reduce_batch_kernels.hpp" in mk
-    inc = open(os.path.join(ROOT, "tests", "cpp", "reduce_batch.mk")).read()
-    assert "include batch.mk" in inc and "test_batch_reduce_api" in inc

@@ -162,10 +162,6 @@ def test_the_standalone_header_is_generated_and_compiles(tmp_path):
 def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "Makefile")).read()
     assert "glu_select" in mk and "select_kernels.hpp" in mk and "glu_select_object.hpp" in mk
-    inc = open(os.path.join(ROOT, "tests", "cpp", "select.mk")).read()
-    assert "include key_runs.mk" in inc and "test_select_api" in inc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "select.mk" in entry
 
 
 def test_every_new_kernel_is_built_for_the_five_stencil_types_without_scratch(built):

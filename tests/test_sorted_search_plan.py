@@ -183,10 +183,6 @@ def test_the_standalone_header_is_generated_and_compiles(tmp_path):
 def test_the_library_makefile_and_the_build_know_the_new_unit():
     mk = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "Makefile")).read()
     assert "glu_sorted_search" in mk and "sorted_search_kernels.hpp" in mk and "glu_sorted_search_object.hpp" in mk
-    inc = open(os.path.join(ROOT, "tests", "cpp", "sorted_search.mk")).read()
-    assert "include select.mk" in inc and "test_sorted_search_api" in inc
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "sorted_search.mk" in entry
 
 
 def test_the_index_and_search_kernels_are_built_for_both_key_widths_without_scratch(built):
