@@ -1,6 +1,6 @@
 // glu_host.hpp -- what the translation units of libglu_hip.so share on the HOST side: the error slot behind glu_last_error(), the
 // one device of the process and its queue, the buffer registry behind the glu_buffer handles, grow-only scratch allocations.
-// Defined in glu_core.hip.  The library is built from fifteen translation units (round 6; it was one, a three-minute compile):
+// Defined in glu_core.hip.  The library is built from sixteen translation units (round 6; it was one, a three-minute compile):
 //   glu_core.hip              errors, device, buffers, timer
 //   glu_hip.hip               RadixSort's launch sequences, the segmented sort and the sharded sort (glu_dist_impl.hpp)
 //   glu_sort_passes_u32.hip   the launchers of one counting pass for 4-byte keys (glu_sort_passes.hpp over glu_sort_object.hpp)
@@ -16,9 +16,11 @@
 //   glu_merge.hip             merge: two sorted arrays of keys and values into one, stable (merge_kernels.hpp over merge_path.hpp)
 //   glu_histogram.hip         histogram: counts per bin over even bins or sorted edges (histogram_kernels.hpp over histogram_bins.hpp)
 //   glu_expand.hip            expand: segment, rank and item per element from the offsets (expand_kernels.hpp over expand_path.hpp)
+//   glu_top_k.hip             top-k: the k smallest or largest keys and their indices by a radix select (topk_kernels.hpp over topk_pick.hpp)
 // The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
-// Key runs, select, sorted search, merge, histogram and expand share glu_tile_host.hpp on the host side; the first three and histogram share
-// tile_span.hpp (the tiles, the packs of an array at any alignment) on both sides.
+// Key runs, select, sorted search, merge, histogram, expand and top-k share glu_tile_host.hpp on the host side; the first three, histogram
+// and top-k share tile_span.hpp (the tiles, the packs of an array at any alignment) on both sides; histogram and top-k share the counting
+// walk of histogram_walk.hpp.
 // The argument rules every unit checks by (key types, limits, overlap, alignment, items, handles, out-parameters) are glu_args.hpp's,
 // plain C++ that this header includes; the life of an operator object that owns only scratch is create_object / destroy_object below.
 #pragma once

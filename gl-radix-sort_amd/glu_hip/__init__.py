@@ -22,6 +22,8 @@ SelectStencil_Float, SelectStencil_Double, SelectStencil_Int, SelectStencil_Uint
 SelectOperator_EQ, SelectOperator_NE, SelectOperator_LT, SelectOperator_LE, SelectOperator_GT, SelectOperator_GE = range(6)
 # glu_sorted_search_set_option("PATH", ...) and what glu_sorted_search_plan / glu_sorted_search_last report
 SearchPath_Auto, SearchPath_Direct, SearchPath_Indexed = range(3)
+# glu_top_k_set_option("PATH", ...) and what glu_top_k_read_last reports
+TopKPath_Auto, TopKPath_Candidates, TopKPath_Full = range(3)
 KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2, "uint64": 3, "int64": 4, "float64": 5}  # glu_key_type by numpy dtype name
 
 GLU_OK = 0
@@ -143,6 +145,14 @@ SYMBOLS = [
     ("glu_expand_run_ptr", _int, [_vp, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("glu_expand_plan", _int, [_sz, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_expand_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_top_k_create", _int, [_P(_vp)]),
+    ("glu_top_k_destroy", _int, [_vp]),
+    ("glu_top_k_prepare", _int, [_vp, _sz, _sz, _int]),
+    ("glu_top_k_set_option", _int, [_vp, ctypes.c_char_p, ctypes.c_longlong]),
+    ("glu_top_k_run_ptr", _int, [_vp, _vp, _int, _sz, _sz, _int, _int, _vp, _vp, _vp, _vp]),
+    ("glu_top_k_read_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_top_k_plan", _int, [_sz, _sz, _int, _int, _int, _int, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32),
+                              _P(_sz)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -386,6 +396,18 @@ def plan_expand(total, num_segments):
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_expand_plan(total, num_segments, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
+
+
+def plan_top_k(count, k, key_type="uint32", sorted=True, with_arrays=True, path=TopKPath_Auto, cand_capacity=0):
+    """What a top-k of `k` of `count` keys does (glu_top_k_plan; host only): {"rounds", "digits": [(shift, bits) per round], "tile",
+    "tiles" (glu_select_plan's for the key width), "capacity" (candidates kept), "kernels", "scratch_bytes"}."""
+    rounds, tile, tiles, cap, kernels, scratch = _u32(), _u32(), _u32(), _u32(), _u32(), _sz()
+    shift, bits = (_u32 * 6)(), (_u32 * 6)()
+    check(lib().glu_top_k_plan(count, k, KEY_TYPES[key_type], 1 if sorted else 0, 1 if with_arrays else 0, path, cand_capacity,
+                               ctypes.byref(rounds), shift, bits, ctypes.byref(tile), ctypes.byref(tiles), ctypes.byref(cap),
+                               ctypes.byref(kernels), ctypes.byref(scratch)))
+    return {"rounds": rounds.value, "digits": [(shift[r], bits[r]) for r in range(rounds.value)], "tile": tile.value, "tiles": tiles.value,
+            "capacity": cap.value, "kernels": kernels.value, "scratch_bytes": scratch.value}
 
 
 def _read_batch(fn, handle):
@@ -778,6 +800,41 @@ class Expand(_Handle):
         a, b = _u32(), _u32()
         check(lib().glu_expand_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+
+class TopK(_Handle):
+    """glu::TopK (not in the reference) over the C ABI: the k smallest or largest keys and their indices by a radix select, in the
+    sort's order (floats by their bits), equal keys by ascending index."""
+
+    _CREATE, _DESTROY = "glu_top_k_create", "glu_top_k_destroy"
+
+    def __init__(self, options=None):
+        """options: {"PATH": TopKPath_*, "CAND_CAPACITY": n} (glu_top_k_set_option)."""
+        self._create()
+        for name, value in (options or {}).items():
+            self.set_option(name, value)
+
+    def set_option(self, name, value):
+        check(lib().glu_top_k_set_option(self._h, str(name).encode(), int(value)))
+
+    def prepare(self, count, max_k, key_type="uint32"):
+        """Scratch for calls of up to `count` keys and k up to `max_k` under the options set now: they allocate nothing (capturable)
+        (glu_top_k_prepare)."""
+        check(lib().glu_top_k_prepare(self._h, count, max_k, KEY_TYPES[key_type]))
+
+    def run_ptr(self, keys_ptr, count, k, out_keys_ptr=None, out_indices_ptr=None, out_kth_ptr=None, key_type="uint32", largest=False,
+                sorted=True, stream=None):
+        """The k smallest (largest) of `count` keys: out_keys[0 .. k) bit for bit, out_indices[0 .. k) uint32, *out_kth the k-th best
+        key; each may be None, not all.  sorted: best first, else ascending indices.  All pointers are device pointers; the keys are
+        only read (glu_top_k_run_ptr)."""
+        check(lib().glu_top_k_run_ptr(self._h, _vp(keys_ptr), KEY_TYPES[key_type], count, k, 1 if largest else 0, 1 if sorted else 0,
+                                      _vp(out_keys_ptr), _vp(out_indices_ptr), _vp(out_kth_ptr), _vp(stream)))
+
+    def read_last(self):
+        """{path, candidates, ties, kernels} of the last run_ptr, read back from the device (glu_top_k_read_last); synchronise first."""
+        a, b, c, d = _u32(), _u32(), _u32(), _u32()
+        check(lib().glu_top_k_read_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return {"path": a.value, "candidates": b.value, "ties": c.value, "kernels": d.value}
 
 
 def _check_composed_runs(max_runs):

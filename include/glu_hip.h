@@ -905,6 +905,87 @@ GLU_API glu_status glu_expand_plan(size_t total, size_t num_segments, uint32_t* 
  * where the call had nothing to do). */
 GLU_API glu_status glu_expand_last(glu_expand expand, uint32_t* tiles, uint32_t* kernels);
 
+/* ---- top-k (not in the reference): the k smallest or the k largest of `count` keys and their indices, by a radix select, on the
+ * device and on the caller's stream.  Nearest neighbours, beam search, a threshold at a quantile, the heaviest groups after a
+ * batched reduce.  The keys are only READ (four times where they are spread out); nothing of size `count` is written.
+ *   - `keys`: count keys of one of the six glu_key_type's, on the device, READ ONLY, in any order.  k, largest (0 = smallest) and
+ *     sorted are host values.
+ *   - THE ORDER IS THE SORT'S: the total order on bits that glu_radix_sort_run_typed_ptr produces.  -0.0 < +0.0, and the NaNs lie
+ *     beyond the infinities of their sign, ordered by their payloads.  This is the choice of sorted search and merge, and
+ *     deliberately NOT the IEEE comparison of select (glu_select_run_ptr): the result is a prefix of a sort, not a comparison
+ *     with a value.
+ *   - WHAT IS CHOSEN.  smallest: the first k elements of the stable ascending sort of (key, index).  largest: the first k elements
+ *     of the stable sort by DESCENDING key, equal keys still by ASCENDING index.  One answer for every input: among equal keys
+ *     at the threshold the lowest indices win.  With code() the sort's key code (complemented for largest), in numpy:
+ *     numpy.argsort(code(keys), kind="stable")[:k].
+ *   - OUTPUT ORDER.  sorted != 0: in that order, best first.  sorted == 0: the same k elements in ascending order of their index,
+ *     as select writes them; the final ordering is skipped.
+ *   - OUTPUTS, each optional.  out_keys: the keys, bit for bit.  out_indices: their uint32 indices.  out_kth: ONE key on the
+ *     device, the k-th best, which is the threshold (a median, a quantile).  Exactly k entries of each given array are written
+ *     and nothing behind them.  With both arrays NULL and out_kth given the call is an order statistic and enqueues no compaction
+ *     and no ordering.  All three NULL is refused.
+ *   - Limits: count < 2^32 (the tile layer's); k <= count; k == 0 writes nothing, out_kth neither; count == 0 requires k == 0 and
+ *     accepts NULL keys.  keys, out_keys and out_kth are aligned to the key size, out_indices to 4 bytes.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: a NULL object; NULL keys
+ *     with count > 0; a bad key type; the limits above; misalignment; all outputs NULL; an output overlapping keys or another
+ *     output (arrays that merely touch are fine).  A refused call writes nothing.
+ *   - HOW.  The key code turns every case into "the k smallest unsigned words".  Digits are taken from the top, 11 bits each
+ *     (11 + 11 + 10 for 4-byte keys, 5 x 11 + 9 for 8-byte keys); a small record on the device holds the prefix fixed so far, how
+ *     many words are still needed among those that match it, and how many lie in front.  Round 1 counts the top digit of every
+ *     key (tables in LDS, one row per workgroup, the columns summed, one workgroup picks the digit at which the cumulative count
+ *     reaches k).  Then, decided ON THE DEVICE: GLU_TOP_K_PATH_CANDIDATES where the bucket of that digit holds at most
+ *     CAND_CAPACITY keys (default max(2^16, ceil(count / 512)); uniform keys fill count / 2048): one more read appends the
+ *     matching code words to the object's scratch and one workgroup runs the remaining rounds over them; else GLU_TOP_K_PATH_FULL:
+ *     every remaining round reads the input again, filtered by the prefix (all keys equal, few distinct values).  Both chains are
+ *     always enqueued; the kernels of the one not taken return at once.  The compaction counts per tile the keys below the
+ *     threshold and the keys equal to it, scans both (the count scan of key runs and select) and writes every key below and the
+ *     first `ties` equal ones at their ranks: ascending indices, exactly k.  sorted != 0: (code word, index) pairs go to scratch,
+ *     the object's own glu_radix_sort orders them (unsigned, stable), a small kernel decodes them into the outputs.
+ *   - THE ONE ATOMIC on device memory is the append of the candidates: a workgroup holds its candidates in LDS and adds their number
+ *     to one word whenever it holds more than a tile's worth, and at its end.  Their order is arbitrary and does not matter: only
+ *     counts are taken from them, and integer counts commute.  THE SAME INPUT GIVES THE SAME BITS EVERY TIME.
+ *   - The call only enqueues on `stream`: no host synchronisation, no side stream, no read-back, and no device allocation once
+ *     glu_top_k_prepare covered (count, max_k, key_type) under the options set (else grow-only allocation inside the call: not
+ *     capturable).  The launch sequence follows from count, k, the key type, sorted, which outputs are given, the address of keys
+ *     and the options, never from the data: a captured call (one stream, no parallel branches) replays on any contents. */
+typedef struct glu_top_k_s* glu_top_k;
+enum
+{
+    GLU_TOP_K_PATH_AUTO = 0,   /* an option only: the device decides */
+    GLU_TOP_K_PATH_CANDIDATES, /* as AUTO (a bucket that does not fit still falls back to FULL on the device, and is reported so) */
+    GLU_TOP_K_PATH_FULL        /* the candidate chain is not enqueued */
+};
+/* Not in the reference. */
+GLU_API glu_status glu_top_k_create(glu_top_k* out);
+/* Not in the reference. */
+GLU_API glu_status glu_top_k_destroy(glu_top_k top_k);
+/* Not in the reference.  Grow-only scratch (glu_top_k_plan's scratch_bytes, and the object's sort prepared for max_k pairs) for calls
+ * of up to `count` keys of the width of `key_type` and k up to max_k, under the options set now: after it such a call allocates
+ * nothing (and can be captured). */
+GLU_API glu_status glu_top_k_prepare(glu_top_k top_k, size_t count, size_t max_k, glu_key_type key_type);
+/* Not in the reference.  "PATH": GLU_TOP_K_PATH_AUTO, _CANDIDATES or _FULL.  "CAND_CAPACITY": the candidates the object keeps, 1 ..
+ * 2^30, or 0 for the default of the count.  Both exist so that tests reach both paths at small sizes.  Anything else is refused. */
+GLU_API glu_status glu_top_k_set_option(glu_top_k top_k, const char* name, long long value);
+/* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_top_k_run_ptr(glu_top_k top_k, const void* keys, glu_key_type key_type, size_t count, size_t k, int largest,
+                                     int sorted, void* out_keys, uint32_t* out_indices, void* out_kth, void* stream);
+/* Not in the reference.  For a caller who has synchronised the stream, like glu_radix_sort_read_finish, and the only function of the
+ * operator that reads back: what the object's last run_ptr did.  path = GLU_TOP_K_PATH_CANDIDATES or _FULL, as the device chose after
+ * round 1; candidates = the code words collected (0 on FULL); ties = the keys equal to the threshold that were taken (1 .. k);
+ * kernels = the kernels enqueued, the internal sort counted as one.  All 0 where the call had k == 0.  Any pointer may be NULL. */
+GLU_API glu_status glu_top_k_read_last(glu_top_k top_k, uint32_t* path, uint32_t* candidates, uint32_t* ties, uint32_t* kernels);
+/* Not in the reference.  Host only, no device, pure.  For a call of `count` keys and `k` with the arrays given or not (with_arrays:
+ * out_keys or out_indices), under PATH = path and CAND_CAPACITY = cand_capacity (0: the default): rounds = 3 or 6; digit_shift[r],
+ * digit_bits[r] for r < rounds (room for 6): round r takes the bits [shift, shift + bits) of the code word; tile, tiles = those of
+ * glu_select_plan for a stencil of the key's width; capacity = the candidates kept; kernels = 3 for round 1, + 2 for the candidate
+ * chain (not under _PATH_FULL), + 3 for every remaining round over the input, + 4 for the compaction (with_arrays), + 2 for the
+ * ordering (with_arrays and sorted); 0 where count or k is 0.  scratch_bytes = what glu_top_k_prepare(count, k, key_type) reserves
+ * besides the internal sort: the state and the column sums, min(tiles, 1024) rows of 2048 counters, capacity code words, two counts
+ * per tile (and one tile more), k pairs.  Any pointer may be NULL. */
+GLU_API glu_status glu_top_k_plan(size_t count, size_t k, glu_key_type key_type, int sorted, int with_arrays, int path,
+                                  size_t cand_capacity, uint32_t* rounds, uint32_t* digit_shift, uint32_t* digit_bits, uint32_t* tile,
+                                  uint32_t* tiles, uint32_t* capacity, uint32_t* kernels, size_t* scratch_bytes);
+
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
  * sharded form of glu::RadixSort::operator() (glu/RadixSort.hpp:273-334) that BASELINE.json configs[3] asks for.
