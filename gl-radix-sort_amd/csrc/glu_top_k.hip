@@ -189,7 +189,14 @@ glu_status glu_top_k_set_option(glu_top_k top_k, const char* name, long long val
         top_k->capacity = (uint32_t) value;
         return GLU_OK;
     }
-    return fail(GLU_ERROR_INVALID_ARGUMENT, "Unknown option: %s (the options are PATH and CAND_CAPACITY)", name);
+    if (!strcmp(name, "BATCH_LOOP_MIN")) // (the batched calls, glu_top_k_batch.hip)
+    {
+        if (value < 0 || value >= (long long) 1 << 32)
+            return fail(GLU_ERROR_INVALID_ARGUMENT, "BATCH_LOOP_MIN must lie in [0, 2^32), 0 being the default (got %lld)", value);
+        top_k->batch_loop_min = (uint64_t) value;
+        return GLU_OK;
+    }
+    return fail(GLU_ERROR_INVALID_ARGUMENT, "Unknown option: %s (the options are PATH, CAND_CAPACITY and BATCH_LOOP_MIN)", name);
 }
 
 glu_status glu_top_k_prepare(glu_top_k top_k, size_t count, size_t max_k, glu_key_type key_type)

@@ -67,6 +67,91 @@ namespace glu
             kth(keys.device_ptr(), count, k, out_kth.device_ptr(), GLU_KEY_UINT32, from_largest);
         }
 
+        /// ---- batched: the k best keys of every segment in one call (glu_top_k_run_batch_ptr / _batch_offsets_ptr in glu_hip.h).
+        /// Outputs are rows of stride k; indices are local to the segment; out_kth holds one key per segment.  Each output may be
+        /// nullptr, not all three.  With offsets, a segment shorter than k fills only its first min(k, length) entries.
+        void prepare_batch(size_t total, size_t num_segments, size_t max_k, glu_key_type key_type = GLU_KEY_UINT32)
+        {
+            GLU_CHECK_STATUS(glu_top_k_prepare_batch(m_impl, total, num_segments, max_k, key_type));
+        }
+        void smallest_batch(const void* device_keys, size_t count, size_t num_partitions, size_t k, void* device_out_keys,
+                            uint32_t* device_out_indices, glu_key_type key_type = GLU_KEY_UINT32, bool sorted = true,
+                            void* device_out_kth = nullptr, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_ptr(m_impl, device_keys, key_type, count, num_partitions, k, 0, sorted ? 1 : 0, device_out_keys,
+                                                     device_out_indices, device_out_kth, stream));
+        }
+        void largest_batch(const void* device_keys, size_t count, size_t num_partitions, size_t k, void* device_out_keys,
+                           uint32_t* device_out_indices, glu_key_type key_type = GLU_KEY_UINT32, bool sorted = true,
+                           void* device_out_kth = nullptr, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_ptr(m_impl, device_keys, key_type, count, num_partitions, k, 1, sorted ? 1 : 0, device_out_keys,
+                                                     device_out_indices, device_out_kth, stream));
+        }
+        void kth_batch(const void* device_keys, size_t count, size_t num_partitions, size_t k, void* device_out_kth,
+                       glu_key_type key_type = GLU_KEY_UINT32, bool from_largest = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_ptr(m_impl, device_keys, key_type, count, num_partitions, k, from_largest ? 1 : 0, 0, nullptr,
+                                                     nullptr, device_out_kth, stream));
+        }
+        /// device_offsets: num_segments + 1 uint32 on the device, as glu::KeyRuns writes them.
+        void smallest_batch_offsets(const void* device_keys, size_t total, const uint32_t* device_offsets, size_t num_segments, size_t k,
+                                    void* device_out_keys, uint32_t* device_out_indices, glu_key_type key_type = GLU_KEY_UINT32,
+                                    bool sorted = true, void* device_out_kth = nullptr, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_offsets_ptr(m_impl, device_keys, key_type, total, device_offsets, num_segments, k, 0,
+                                                             sorted ? 1 : 0, device_out_keys, device_out_indices, device_out_kth, stream));
+        }
+        void largest_batch_offsets(const void* device_keys, size_t total, const uint32_t* device_offsets, size_t num_segments, size_t k,
+                                   void* device_out_keys, uint32_t* device_out_indices, glu_key_type key_type = GLU_KEY_UINT32,
+                                   bool sorted = true, void* device_out_kth = nullptr, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_offsets_ptr(m_impl, device_keys, key_type, total, device_offsets, num_segments, k, 1,
+                                                             sorted ? 1 : 0, device_out_keys, device_out_indices, device_out_kth, stream));
+        }
+        void kth_batch_offsets(const void* device_keys, size_t total, const uint32_t* device_offsets, size_t num_segments, size_t k,
+                               void* device_out_kth, glu_key_type key_type = GLU_KEY_UINT32, bool from_largest = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_top_k_run_batch_offsets_ptr(m_impl, device_keys, key_type, total, device_offsets, num_segments, k,
+                                                             from_largest ? 1 : 0, 0, nullptr, nullptr, device_out_kth, stream));
+        }
+        /// uint32 keys in buffers, from their starts.
+        void smallest_batch(const ShaderStorageBuffer& keys, size_t count, size_t num_partitions, size_t k, ShaderStorageBuffer& out_keys,
+                            ShaderStorageBuffer& out_indices, bool sorted = true)
+        {
+            smallest_batch(keys.device_ptr(), count, num_partitions, k, out_keys.device_ptr(), (uint32_t*) out_indices.device_ptr(), GLU_KEY_UINT32,
+                           sorted);
+        }
+        void largest_batch(const ShaderStorageBuffer& keys, size_t count, size_t num_partitions, size_t k, ShaderStorageBuffer& out_keys,
+                           ShaderStorageBuffer& out_indices, bool sorted = true)
+        {
+            largest_batch(keys.device_ptr(), count, num_partitions, k, out_keys.device_ptr(), (uint32_t*) out_indices.device_ptr(), GLU_KEY_UINT32,
+                          sorted);
+        }
+        void smallest_batch_offsets(const ShaderStorageBuffer& keys, size_t total, const ShaderStorageBuffer& offsets, size_t num_segments,
+                                    size_t k, ShaderStorageBuffer& out_keys, ShaderStorageBuffer& out_indices, bool sorted = true)
+        {
+            smallest_batch_offsets(keys.device_ptr(), total, (const uint32_t*) offsets.device_ptr(), num_segments, k, out_keys.device_ptr(),
+                                   (uint32_t*) out_indices.device_ptr(), GLU_KEY_UINT32, sorted);
+        }
+        void largest_batch_offsets(const ShaderStorageBuffer& keys, size_t total, const ShaderStorageBuffer& offsets, size_t num_segments,
+                                   size_t k, ShaderStorageBuffer& out_keys, ShaderStorageBuffer& out_indices, bool sorted = true)
+        {
+            largest_batch_offsets(keys.device_ptr(), total, (const uint32_t*) offsets.device_ptr(), num_segments, k, out_keys.device_ptr(),
+                                  (uint32_t*) out_indices.device_ptr(), GLU_KEY_UINT32, sorted);
+        }
+        /// The segments of the last batched call per class and the kernels it enqueued: synchronise first.
+        struct LastBatch
+        {
+            uint32_t wave_segments = 0, block_segments = 0, long_segments = 0, kernels = 0;
+        };
+        [[nodiscard]] LastBatch read_batch() const
+        {
+            LastBatch l;
+            GLU_CHECK_STATUS(glu_top_k_read_batch(m_impl, &l.wave_segments, &l.block_segments, &l.long_segments, &l.kernels));
+            return l;
+        }
+
         /// What a call with these sizes does (glu_top_k_plan; host only, no device needed).
         struct Plan
         {

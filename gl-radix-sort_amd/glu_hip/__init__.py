@@ -153,6 +153,12 @@ SYMBOLS = [
     ("glu_top_k_read_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_top_k_plan", _int, [_sz, _sz, _int, _int, _int, _int, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32),
                               _P(_sz)]),
+    ("glu_top_k_run_batch_ptr", _int, [_vp, _vp, _int, _sz, _sz, _sz, _int, _int, _vp, _vp, _vp, _vp]),
+    ("glu_top_k_run_batch_offsets_ptr", _int, [_vp, _vp, _int, _sz, _vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _vp]),
+    ("glu_top_k_prepare_batch", _int, [_vp, _sz, _sz, _sz, _int]),
+    ("glu_top_k_plan_batch", _int, [_sz, _sz, _sz, _int, _int, _int, _int, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz),
+                                    _P(_u32), _P(_sz)]),
+    ("glu_top_k_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_dist_available", _int, []),
     ("glu_dist_unique_id", _int, [_vp, _sz]),
     ("glu_dist_create", _int, [_vp, _sz, _int, _int, _P(_vp)]),
@@ -408,6 +414,23 @@ def plan_top_k(count, k, key_type="uint32", sorted=True, with_arrays=True, path=
                                ctypes.byref(kernels), ctypes.byref(scratch)))
     return {"rounds": rounds.value, "digits": [(shift[r], bits[r]) for r in range(rounds.value)], "tile": tile.value, "tiles": tiles.value,
             "capacity": cap.value, "kernels": kernels.value, "scratch_bytes": scratch.value}
+
+
+# glu_top_k_plan_batch's path
+TopKBatch_None, TopKBatch_Wave, TopKBatch_Block, TopKBatch_Long, TopKBatch_Loop, TopKBatch_Binned = range(6)
+
+
+def plan_top_k_batch(count, num_segments, k, key_type="uint32", offsets_form=False, sorted=True, with_arrays=True, loop_min=0):
+    """What a batched top-k does (glu_top_k_plan_batch; host only).  count: keys per partition, or the batch's total with
+    offsets_form.  {"path" (TopKBatch_*), "tile", "limits" (longest segment of the wave class and the three workgroup tiles),
+    "wave_digit_bits", "cand_room", "loop_min", "kernels", "scratch_bytes"}: the single statement of the provisional class limits."""
+    path, tile, bits, room, kernels, loop, scratch = _u32(), _u32(), _u32(), _u32(), _u32(), _sz(), _sz()
+    limits = (_u32 * 4)()
+    check(lib().glu_top_k_plan_batch(count, num_segments, k, KEY_TYPES[key_type], 1 if offsets_form else 0, 1 if sorted else 0,
+                                     1 if with_arrays else 0, loop_min, ctypes.byref(path), ctypes.byref(tile), limits, ctypes.byref(bits),
+                                     ctypes.byref(room), ctypes.byref(loop), ctypes.byref(kernels), ctypes.byref(scratch)))
+    return {"path": path.value, "tile": tile.value, "limits": list(limits), "wave_digit_bits": bits.value, "cand_room": room.value,
+            "loop_min": loop.value, "kernels": kernels.value, "scratch_bytes": scratch.value}
 
 
 def _read_batch(fn, handle):
@@ -809,7 +832,7 @@ class TopK(_Handle):
     _CREATE, _DESTROY = "glu_top_k_create", "glu_top_k_destroy"
 
     def __init__(self, options=None):
-        """options: {"PATH": TopKPath_*, "CAND_CAPACITY": n} (glu_top_k_set_option)."""
+        """options: {"PATH": TopKPath_*, "CAND_CAPACITY": n, "BATCH_LOOP_MIN": n} (glu_top_k_set_option)."""
         self._create()
         for name, value in (options or {}).items():
             self.set_option(name, value)
@@ -835,6 +858,35 @@ class TopK(_Handle):
         a, b, c, d = _u32(), _u32(), _u32(), _u32()
         check(lib().glu_top_k_read_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
         return {"path": a.value, "candidates": b.value, "ties": c.value, "kernels": d.value}
+
+    def prepare_batch(self, total, num_segments, max_k, key_type="uint32"):
+        """Scratch for batched calls of up to `total` keys in up to `num_segments` segments and k up to `max_k` under the options set
+        now: they allocate nothing (capturable) (glu_top_k_prepare_batch)."""
+        check(lib().glu_top_k_prepare_batch(self._h, total, num_segments, max_k, KEY_TYPES[key_type]))
+
+    def run_batch_ptr(self, keys_ptr, count, num_partitions, k, out_keys_ptr=None, out_indices_ptr=None, out_kth_ptr=None, key_type="uint32",
+                      largest=False, sorted=True, stream=None):
+        """The k best keys of each of `num_partitions` partitions of `count` keys: rows of stride k of out_keys (bit for bit) and
+        out_indices (uint32, local to the partition), out_kth[s] the k-th best of partition s; each may be None, not all
+        (glu_top_k_run_batch_ptr)."""
+        check(lib().glu_top_k_run_batch_ptr(self._h, _vp(keys_ptr), KEY_TYPES[key_type], count, num_partitions, k, 1 if largest else 0,
+                                            1 if sorted else 0, _vp(out_keys_ptr), _vp(out_indices_ptr), _vp(out_kth_ptr), _vp(stream)))
+
+    def run_batch_offsets_ptr(self, keys_ptr, total, offsets_ptr, num_segments, k, out_keys_ptr=None, out_indices_ptr=None, out_kth_ptr=None,
+                              key_type="uint32", largest=False, sorted=True, stream=None):
+        """... of the segments [offsets[s], offsets[s + 1]) of a device array of num_segments + 1 uint32, k_s = min(k, length) per
+        segment; the entries j >= k_s of a row and the out_kth of an empty segment are not touched
+        (glu_top_k_run_batch_offsets_ptr)."""
+        check(lib().glu_top_k_run_batch_offsets_ptr(self._h, _vp(keys_ptr), KEY_TYPES[key_type], total, _vp(offsets_ptr), num_segments, k,
+                                                    1 if largest else 0, 1 if sorted else 0, _vp(out_keys_ptr), _vp(out_indices_ptr),
+                                                    _vp(out_kth_ptr), _vp(stream)))
+
+    def read_batch(self):
+        """{wave, block, long, kernels} of the last batched call: its segments per class and the kernels it enqueued
+        (glu_top_k_read_batch); synchronise first."""
+        a, b, c, d = _u32(0), _u32(0), _u32(0), _u32(0)
+        check(lib().glu_top_k_read_batch(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return {"wave": a.value, "block": b.value, "long": c.value, "kernels": d.value}
 
 
 def _check_composed_runs(max_runs):

@@ -964,7 +964,9 @@ GLU_API glu_status glu_top_k_destroy(glu_top_k top_k);
  * nothing (and can be captured). */
 GLU_API glu_status glu_top_k_prepare(glu_top_k top_k, size_t count, size_t max_k, glu_key_type key_type);
 /* Not in the reference.  "PATH": GLU_TOP_K_PATH_AUTO, _CANDIDATES or _FULL.  "CAND_CAPACITY": the candidates the object keeps, 1 ..
- * 2^30, or 0 for the default of the count.  Both exist so that tests reach both paths at small sizes.  Anything else is refused. */
+ * 2^30, or 0 for the default of the count.  "BATCH_LOOP_MIN": equal partitions of a batched call of at least this many keys go
+ * through the single call one by one, 0 .. 2^32 - 1, 0 for the default (2^22: the crossover measured at 64 rows, provisional otherwise).  They exist so that tests
+ * reach every path at small sizes.  Anything else is refused. */
 GLU_API glu_status glu_top_k_set_option(glu_top_k top_k, const char* name, long long value);
 /* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
 GLU_API glu_status glu_top_k_run_ptr(glu_top_k top_k, const void* keys, glu_key_type key_type, size_t count, size_t k, int largest,
@@ -985,6 +987,76 @@ GLU_API glu_status glu_top_k_read_last(glu_top_k top_k, uint32_t* path, uint32_t
 GLU_API glu_status glu_top_k_plan(size_t count, size_t k, glu_key_type key_type, int sorted, int with_arrays, int path,
                                   size_t cand_capacity, uint32_t* rounds, uint32_t* digit_shift, uint32_t* digit_bits, uint32_t* tile,
                                   uint32_t* tiles, uint32_t* capacity, uint32_t* kernels, size_t* scratch_bytes);
+
+/* ---- batched top-k: the k best keys of every segment in one call -----------------------------------------
+ * Not in the reference.  The segments are equal partitions of `count` keys (glu_top_k_run_batch_ptr) or [offsets[s], offsets[s + 1])
+ * of a DEVICE array of num_segments + 1 uint32 that the host never reads (glu_top_k_run_batch_offsets_ptr, as glu_key_runs writes
+ * it); a segment that ends below its begin or beyond `total` is empty to every kernel.  `keys` are only read; all six key types.
+ *   - WHAT IS CHOSEN.  The contract of glu_top_k_run_ptr applied to each segment with k_s = min(k, its length): with code() the
+ *     sort's key code (complemented for largest), numpy.argsort(code(segment), kind="stable")[:k_s].  sorted != 0: best first, else
+ *     in ascending order of the index.
+ *   - OUTPUTS, each optional, rows of stride k.  out_keys[s * k + j]: the keys, bit for bit.  out_indices[s * k + j]: uint32 indices
+ *     LOCAL to the segment (relative to offsets[s]), as torch.topk along a dimension gives.  out_kth[s]: the k_s-th best key of
+ *     segment s.  The entries j >= k_s of a row and the out_kth of an empty segment are not touched.  All three NULL is refused.
+ *     k == 0 or num_segments == 0 writes nothing.
+ *   - Limits: total < 2^32; num_segments <= 2^24; num_segments * k < 2^32; equal partitions: k <= count.  keys, out_keys and out_kth
+ *     are aligned to the key size, out_indices and offsets to 4 bytes; no output overlaps keys, offsets or another output.
+ *     GLU_ERROR_INVALID_ARGUMENT with a message that names the argument; a refused call writes nothing.
+ *   - HOW.  Three classes of segments by length (glu_top_k_plan_batch states the limits; ALL OF THEM ARE PROVISIONAL, no class
+ *     limit is placed by a measurement yet): up to 512 keys a WAVE per segment holds them in registers and selects with 8-bit digits on a wave-private row
+ *     of counters in LDS; up to 8 / 32 / 128 KiB of keys a WORKGROUP reads the segment once into LDS and runs every 11-bit round
+ *     there; a longer segment is streamed by one workgroup (round 1 over the segment; then the threshold's bucket is collected into
+ *     LDS where it fits, cand_room keys, else every round reads the segment again).  Equal partitions: the host picks the one class
+ *     kernel (path GLU_TOP_K_BATCH_WAVE / _BLOCK / _LONG); partitions of at least BATCH_LOOP_MIN keys (glu_top_k_set_option; 0: the
+ *     default) go through glu_top_k_run_ptr one after the other (GLU_TOP_K_BATCH_LOOP), each filling the device by itself.  Device
+ *     offsets (GLU_TOP_K_BATCH_BINNED): a binning kernel appends every non-empty segment to the list of its class, one kernel per
+ *     class walks its list.  sorted with arrays: the class kernels write (code word, local index) rows to scratch, padded behind
+ *     k_s with all-ones codes, the object's own sort orders all rows with ONE glu_radix_sort_run_batch_ptr (stable: ties stay by
+ *     ascending index, pads behind real entries), a decode kernel writes j < k_s of every row.  WHERE k EXCEEDS THE BATCHED SORT'S
+ *     SINGLE-BLOCK LIMIT (glu_radix_sort_plan_batch: path 3) THAT SORT IS ONE ORDINARY SORT PER ROW, and `kernels` counts one per row.
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back, no side stream; after glu_top_k_prepare_batch no
+ *     allocation (capturable as a linear chain).  The launch sequence follows from host values only.  The same input gives the
+ *     same bits every time: the only atomics on device memory are the list appends of the binning kernel, and the order of a list
+ *     does not matter. */
+enum
+{
+    GLU_TOP_K_BATCH_NONE = 0, /* nothing is enqueued: no key, no segment or k == 0 */
+    GLU_TOP_K_BATCH_WAVE,     /* equal partitions on the wave class's kernel */
+    GLU_TOP_K_BATCH_BLOCK,    /* ... on a workgroup tile's kernel */
+    GLU_TOP_K_BATCH_LONG,     /* ... on the streaming kernel */
+    GLU_TOP_K_BATCH_LOOP,     /* ... of at least BATCH_LOOP_MIN keys: the single call, partition after partition */
+    GLU_TOP_K_BATCH_BINNED    /* device offsets: binning, then one kernel per class */
+};
+/* Not in the reference.  Equal partitions: segment s is partition s of `count` keys. */
+GLU_API glu_status glu_top_k_run_batch_ptr(glu_top_k top_k, const void* keys, glu_key_type key_type, size_t count, size_t num_partitions,
+                                           size_t k, int largest, int sorted, void* out_keys, uint32_t* out_indices, void* out_kth,
+                                           void* stream);
+/* Not in the reference.  Device offsets. */
+GLU_API glu_status glu_top_k_run_batch_offsets_ptr(glu_top_k top_k, const void* keys, glu_key_type key_type, size_t total,
+                                                   const uint32_t* offsets, size_t num_segments, size_t k, int largest, int sorted,
+                                                   void* out_keys, uint32_t* out_indices, void* out_kth, void* stream);
+/* Not in the reference.  Grow-only scratch for batched calls of up to `total` keys of the width of `key_type` in up to num_segments
+ * segments with k up to max_k, under the options set now (the list image, the rows of pairs and the object's sort for them, the
+ * single call's scratch where equal partitions of total / num_segments keys take the loop), and the LDS opt-in of the workgroup
+ * kernels: after it such a call allocates nothing. */
+GLU_API glu_status glu_top_k_prepare_batch(glu_top_k top_k, size_t total, size_t num_segments, size_t max_k, glu_key_type key_type);
+/* Not in the reference.  Host only, no device, pure: the single statement of the unmeasured choices.  offsets_form == 0: `count` keys
+ * per partition; else `count` is the batch's total.  loop_min: BATCH_LOOP_MIN, 0 for the default.  path = GLU_TOP_K_BATCH_*; tile =
+ * the class limit the equal partitions run under (0: none); class_limits[0 .. 4) = the longest segment of the wave class and of the
+ * three workgroup tiles for this key width (8-byte keys: half the 4-byte ones, the wave class excepted); wave_digit_bits = the wave
+ * class's digit width; cand_room = keys of the long class's candidate buffer; loop_min_used = the threshold in force; kernels = what
+ * the call enqueues (1 class kernel, or per partition the single call's under LOOP, or the binning kernel and one kernel per list
+ * that can hold a segment; + the sort, counted as one or as one per row, and the decode kernel where sorted with arrays; 0 where
+ * nothing is enqueued); scratch_bytes = the list image and the rows of pairs (LOOP: the single call's).  Any pointer may be NULL. */
+GLU_API glu_status glu_top_k_plan_batch(size_t count, size_t num_segments, size_t k, glu_key_type key_type, int offsets_form, int sorted,
+                                        int with_arrays, size_t loop_min, uint32_t* path, uint32_t* tile, uint32_t* class_limits,
+                                        uint32_t* wave_digit_bits, uint32_t* cand_room, size_t* loop_min_used, uint32_t* kernels,
+                                        size_t* scratch_bytes);
+/* Not in the reference.  For a caller who has synchronised the stream: the segments of the object's last batched call per class (device
+ * offsets: the counts the binning kernel left; equal partitions: the host's own; LOOP counts its partitions as long) and the kernels
+ * it enqueued (the plan's).  Any pointer may be NULL. */
+GLU_API glu_status glu_top_k_read_batch(glu_top_k top_k, uint32_t* wave_segments, uint32_t* block_segments, uint32_t* long_segments,
+                                        uint32_t* kernels);
 
 /* ---- sharded sort over the GPUs of one node ---------------------------------------------------------
  * The reference is single-device (one GL context, no communication code: SURVEY.md section 2 row C1); this is the
