@@ -16,6 +16,7 @@
 //   glu_merge.hip             merge: two sorted arrays of keys and values into one, stable (merge_kernels.hpp over merge_path.hpp)
 //   glu_histogram.hip         histogram: counts per bin over even bins or sorted edges (histogram_kernels.hpp over histogram_bins.hpp)
 //   glu_expand.hip            expand: segment, rank and item per element from the offsets (expand_kernels.hpp over expand_path.hpp)
+//   glu_gather.hip            gather and scatter: items fetched or placed by device indices (gather_kernels.hpp over gather_walk.hpp)
 //   glu_top_k.hip             top-k: the k smallest or largest keys and their indices by a radix select (topk_kernels.hpp over topk_pick.hpp)
 // The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
 // Key runs, select, sorted search, merge, histogram, expand and top-k share glu_tile_host.hpp on the host side; the first three, histogram

@@ -145,6 +145,14 @@ SYMBOLS = [
     ("glu_expand_run_ptr", _int, [_vp, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("glu_expand_plan", _int, [_sz, _sz, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_expand_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_gather_create", _int, [_P(_vp)]),
+    ("glu_gather_destroy", _int, [_vp]),
+    ("glu_gather_run_ptr", _int, [_vp, _vp, _sz, _u32, _vp, _sz, _vp, _vp]),
+    ("glu_gather_run_batch_ptr", _int, [_vp, _vp, _u32, _sz, _sz, _vp, _sz, _vp, _vp]),
+    ("glu_gather_run_batch_offsets_ptr", _int, [_vp, _vp, _u32, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("glu_gather_scatter_ptr", _int, [_vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp]),
+    ("glu_gather_plan", _int, [_sz, _u32, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_gather_last", _int, [_vp, _P(_u32), _P(_u32)]),
     ("glu_top_k_create", _int, [_P(_vp)]),
     ("glu_top_k_destroy", _int, [_vp]),
     ("glu_top_k_prepare", _int, [_vp, _sz, _sz, _int]),
@@ -402,6 +410,15 @@ def plan_expand(total, num_segments):
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_expand_plan(total, num_segments, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
+
+
+def plan_gather(count, item_bytes):
+    """(tile, tiles, kernels) of a gather or a scatter of `count` entries of `item_bytes` (glu_gather_plan; host only): the entries
+    per workgroup, ceil(count / tile) (a call on an array that starts inside a 16-byte pack can take one more), 1 kernel, or 0
+    where count is 0."""
+    a, b, c = _u32(), _u32(), _u32()
+    check(lib().glu_gather_plan(count, item_bytes, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
 
 
 def plan_top_k(count, k, key_type="uint32", sorted=True, with_arrays=True, path=TopKPath_Auto, cand_capacity=0):
@@ -822,6 +839,45 @@ class Expand(_Handle):
         """(tiles, kernels) of what the last run_ptr enqueued (glu_expand_last; no device read)."""
         a, b = _u32(), _u32()
         check(lib().glu_expand_last(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+
+class Gather(_Handle):
+    """glu::Gather (not in the reference) over the C ABI: items of 4, 8, 16 or 32 bytes fetched or placed by uint32 indices on the
+    device.  No index is trusted: an entry whose index is out of range is skipped and its place in `out` is not touched.  The object
+    owns no device memory; every call is allocation-free.  All pointers are device pointers."""
+
+    _CREATE, _DESTROY = "glu_gather_create", "glu_gather_destroy"
+
+    def __init__(self):
+        self._create()
+
+    def run_ptr(self, items_ptr, item_count, item_bytes, indices_ptr, count, out_ptr, stream=None):
+        """out[j] = items[indices[j]] for j < count wherever indices[j] < item_count (glu_gather_run_ptr)."""
+        check(lib().glu_gather_run_ptr(self._h, _vp(items_ptr), item_count, item_bytes, _vp(indices_ptr), count, _vp(out_ptr), _vp(stream)))
+
+    def run_batch_ptr(self, items_ptr, item_bytes, count, num_partitions, indices_ptr, k, out_ptr, stream=None):
+        """Rows of stride k of indices local to equal partitions of `count` items, what TopK.run_batch_ptr writes:
+        out[s * k + j] = items[s * count + indices[s * k + j]] for j < min(k, count) (glu_gather_run_batch_ptr)."""
+        check(lib().glu_gather_run_batch_ptr(self._h, _vp(items_ptr), item_bytes, count, num_partitions, _vp(indices_ptr), k, _vp(out_ptr),
+                                             _vp(stream)))
+
+    def run_batch_offsets_ptr(self, items_ptr, item_bytes, total, offsets_ptr, num_segments, indices_ptr, k, out_ptr, stream=None):
+        """... local to the segments [offsets[s], offsets[s + 1]) of a device array of num_segments + 1 uint32; the entries
+        j >= min(k, length) of a row are not touched (glu_gather_run_batch_offsets_ptr)."""
+        check(lib().glu_gather_run_batch_offsets_ptr(self._h, _vp(items_ptr), item_bytes, total, _vp(offsets_ptr), num_segments,
+                                                     _vp(indices_ptr), k, _vp(out_ptr), _vp(stream)))
+
+    def scatter_ptr(self, items_ptr, item_bytes, indices_ptr, count, out_ptr, out_count, stream=None):
+        """out[indices[j]] = items[j] for j < count wherever indices[j] < out_count; the indices are expected to be distinct
+        (glu_gather_scatter_ptr)."""
+        check(lib().glu_gather_scatter_ptr(self._h, _vp(items_ptr), item_bytes, _vp(indices_ptr), count, _vp(out_ptr), out_count,
+                                           _vp(stream)))
+
+    def last(self):
+        """(tiles, kernels) of what the last call enqueued (glu_gather_last; no device read)."""
+        a, b = _u32(), _u32()
+        check(lib().glu_gather_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
 

@@ -732,9 +732,9 @@ GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* pa
  *     pointer of a side with elements; a mix of NULL and non-NULL value pointers; misalignment; a bad key type; the limit above; an
  *     output overlapping an input or the other output.  A refused call writes nothing.
  *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge
- *     an iota as the values, and fetch the wide values through the merged iota; the library has no gather by an arbitrary
- *     permutation: glu_expand_run_ptr gathers per SEGMENT, out[j] = items[segment of j], which is that fetch only where the
- *     merged iota is a sequence of runs); set operations; a segmented merge; counts that live on the device. */
+ *     an iota as the values, and fetch the wide values through the merged iota with glu_gather_run_ptr, the gather by an
+ *     arbitrary permutation; it takes one source array, so A's and B's values are copied into one array first); set
+ *     operations; a segmented merge; counts that live on the device. */
 typedef struct glu_merge_s* glu_merge;
 /* Not in the reference. */
 GLU_API glu_status glu_merge_create(glu_merge* out);
@@ -883,7 +883,8 @@ GLU_API glu_status glu_histogram_last(glu_histogram histogram, uint32_t* path, u
  *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: a NULL object; NULL
  *     offsets with work to do; only one of items and out_items; a bad item_bytes; misalignment; the limits above; an output
  *     overlapping offsets, items or another output.  A refused call writes nothing.
- *   - OUT OF SCOPE: a counts-form entry point (the recipe above); items wider than 32 bytes; a gather by an arbitrary permutation;
+ *   - OUT OF SCOPE: a counts-form entry point (the recipe above); items wider than 32 bytes; a gather by an arbitrary permutation (that is
+ *     glu_gather_run_ptr);
  *     a segmented select that rewrites offsets; 64-bit offsets. */
 typedef struct glu_expand_s* glu_expand;
 /* Not in the reference. */
@@ -904,6 +905,74 @@ GLU_API glu_status glu_expand_plan(size_t total, size_t num_segments, uint32_t* 
 /* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels (0 and 0
  * where the call had nothing to do). */
 GLU_API glu_status glu_expand_last(glu_expand expand, uint32_t* tiles, uint32_t* kernels);
+
+/* ---- gather and scatter (not in the reference): items fetched or placed by uint32 indices that live on the device, on the
+ * caller's stream.  The last step behind every operator that ends in indices: the sort's and merge's uint32 values (sort an iota
+ * beside the keys, then fetch records of any width through it), the out_indices of top-k, batched top-k and select, the positions
+ * of sorted search.  numpy's items[indices] and out[indices] = items.  Per entry it reads 4 bytes of index, moves item_bytes once
+ * in and once out, and nothing else.
+ *   - COMMON TO ALL CALLS.  item_bytes is 4, 8, 16 or 32 (select's and expand's sizes); items are copied bit for bit.  `items` and
+ *     `out` are aligned to min(item_bytes, 16), `indices` and `offsets` to 4 bytes.  The inputs are READ ONLY; `out` must not
+ *     overlap any of them (arrays that merely touch are fine).  NO INDEX IS TRUSTED: an entry whose index fails the call's test is
+ *     skipped, the entry of `out` it would have written is NOT TOUCHED, and nothing outside the arrays as the host values state
+ *     them is read or written.
+ *   - glu_gather_run_ptr: for j < count, if indices[j] < item_count then out[j] = items[indices[j]].  Duplicate indices are fine
+ *     (a broadcast).  count < 2^32, item_count <= 2^32; byte offsets are 64 bits wide (item_count * item_bytes reaches 128 GiB).
+ *   - THE BATCHED FORMS read rows of stride k of indices LOCAL to a segment, exactly what glu_top_k_run_batch_ptr and
+ *     glu_top_k_run_batch_offsets_ptr write, and the segments are theirs: partition s of `count` items each (total = count *
+ *     num_partitions), or [offsets[s], offsets[s + 1]) of a device array the host never reads; a segment that ends below its begin
+ *     or beyond `total` is empty.  With len_s the segment's length and k_s = min(k, len_s): for j < k_s, if indices[s * k + j] <
+ *     len_s then out[s * k + j] = items[begin_s + indices[s * k + j]].  Every other entry of `out` is not touched: the entries
+ *     j >= k_s of a row (batched top-k's own rule) and those whose index is not below len_s.  total < 2^32, num_segments <= 2^24,
+ *     num_segments * k < 2^32.
+ *   - glu_gather_scatter_ptr: for j < count, if indices[j] < out_count then out[indices[j]] = items[j]; entries of `out` that no
+ *     index names are not touched.  The indices are expected to be distinct.  WHERE TWO ARE EQUAL that entry holds one of their
+ *     items, and for 32-byte items possibly a mix of their 16-byte halves: the one place where the result is not determined.
+ *     count < 2^32, out_count <= 2^32.
+ *   - count == 0 enqueues nothing; so do k == 0 or no segment in the batched forms, an empty table (item_count, out_count or total
+ *     of 0: no entry can move) and then no array is looked at (all may be NULL).
+ *   - One kernel per call, in one stream, with one workgroup of 256 per tile.  The STREAMING SIDE (`out` of a gather, `items` of a
+ *     scatter) moves in whole 16-byte packs by contiguous lanes whatever its alignment; a 32-byte item is two packs in two
+ *     neighbouring lanes; only a pack that holds an end of the array or a skipped entry goes element by element.  A lane issues all
+ *     of its index loads, then all of its item loads, then stores.  Indices and the streaming side bypass the caches' retention, so
+ *     that the caches hold the table.  The row of a batched entry is an exact quotient by multiplication.  No scratch, hence no
+ *     prepare: every call is allocation-free and capturable from the first.  No atomics, no LDS, no look-back, no side stream, no
+ *     host synchronisation, no read-back.  The grid follows from the host values and the addresses, never from the data: a captured
+ *     call replays on any contents.  THE SAME INPUT GIVES THE SAME BITS EVERY TIME (a scatter: with distinct indices).
+ *   - What bounds it is the memory system's answer to scattered accesses of item_bytes: a random 4-byte read moves a whole cache
+ *     line for 4 useful bytes unless the table stays in a cache.  profiles/gather/README.md has the measurements.
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: a NULL object; a NULL
+ *     array with work to do; a bad item_bytes; misalignment; the limits above; `out` overlapping an input.  A refused call writes
+ *     nothing.
+ *   - OUT OF SCOPE: items wider than 32 bytes; 64-bit indices; a scatter that reduces colliding items; two source arrays in one
+ *     call (merge's iota over A || B); bucketing the indices by source address before the gather. */
+typedef struct glu_gather_s* glu_gather;
+/* Not in the reference. */
+GLU_API glu_status glu_gather_create(glu_gather* out);
+/* Not in the reference. */
+GLU_API glu_status glu_gather_destroy(glu_gather gather);
+/* Not in the reference.  out[j] = items[indices[j]]: the contract above.  Enqueues on `stream` (NULL: the library's queue) and
+ * returns. */
+GLU_API glu_status glu_gather_run_ptr(glu_gather gather, const void* items, size_t item_count, uint32_t item_bytes,
+                                      const uint32_t* indices, size_t count, void* out, void* stream);
+/* Not in the reference.  Rows of stride k over equal partitions of `count` items. */
+GLU_API glu_status glu_gather_run_batch_ptr(glu_gather gather, const void* items, uint32_t item_bytes, size_t count,
+                                            size_t num_partitions, const uint32_t* indices, size_t k, void* out, void* stream);
+/* Not in the reference.  Rows of stride k over the segments of device offsets. */
+GLU_API glu_status glu_gather_run_batch_offsets_ptr(glu_gather gather, const void* items, uint32_t item_bytes, size_t total,
+                                                    const uint32_t* offsets, size_t num_segments, const uint32_t* indices,
+                                                    size_t k, void* out, void* stream);
+/* Not in the reference.  out[indices[j]] = items[j]: the contract above. */
+GLU_API glu_status glu_gather_scatter_ptr(glu_gather gather, const void* items, uint32_t item_bytes, const uint32_t* indices,
+                                          size_t count, void* out, size_t out_count, void* stream);
+/* Not in the reference.  Host only, no device, pure: tile = entries per workgroup (256 threads x 4 packs of 16 bytes: 4096, 2048,
+ * 1024 and 512 items of 4, 8, 16 and 32 bytes; the 4 is PROVISIONAL: profiles/gather/tile_sizes.txt finds 2, 4 and 8 alike), tiles =
+ * ceil(count / tile), the tiles of `count` entries from an aligned base (a call on an array that starts inside a pack can take one
+ * more), kernels = 1, or 0 where count == 0.  Any pointer may be NULL. */
+GLU_API glu_status glu_gather_plan(size_t count, uint32_t item_bytes, uint32_t* tile, uint32_t* tiles, uint32_t* kernels);
+/* Not in the reference.  What the host enqueued in the object's last call (no device read): the tiles and the kernels (0 and 0
+ * where the call had nothing to do). */
+GLU_API glu_status glu_gather_last(glu_gather gather, uint32_t* tiles, uint32_t* kernels);
 
 /* ---- top-k (not in the reference): the k smallest or the k largest of `count` keys and their indices, by a radix select, on the
  * device and on the caller's stream.  Nearest neighbours, beam search, a threshold at a quantile, the heaviest groups after a
