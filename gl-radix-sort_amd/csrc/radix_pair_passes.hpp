@@ -112,6 +112,8 @@ __global__ __launch_bounds__(1024) void radix_pair_count_kernel(const KeyT* __re
     };
     constexpr int VEC = 16 / sizeof(KeyT);
     using VecT = typename std::conditional<sizeof(KeyT) == 4, uint4, ulonglong2>::type;
+    // (vec_ok is never false, here and in radix_pair4_count_kernel: launch_pass_lines is the only caller of both kernels, it runs only
+    // under lines_applicable, and that wants keys_a and keys_b -- the caller's array and the sort's scratch -- 16-byte aligned)
     const bool vec_ok = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
     const uint64_t nvec = vec_ok ? (end - begin) / VEC : 0;
     const VecT* vkeys = reinterpret_cast<const VecT*>(keys + begin);

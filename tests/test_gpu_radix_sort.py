@@ -562,6 +562,15 @@ def test_typed_keys(G, bits, dtype, n):
         keys[rng.integers(0, n, 2)] = np.inf
         keys[rng.integers(0, n, 2)] = -np.inf
         keys[rng.integers(0, n, max(1, n // 20))] = dt.type(1.5)  # duplicates
+        # NaNs of both signs with two payloads and denormals of both signs: the header promises "NaNs beyond the infinities of their
+        # sign"; the reference image below orders them so
+        tiny = np.finfo(dt).smallest_subnormal
+        ubits = np.uint32 if dt.itemsize == 4 else np.uint64
+        nan = np.array([np.nan], dtype=dt).view(ubits)[0]
+        top = ubits(1) << ubits(dt.itemsize * 8 - 1)
+        nans = np.array([nan, nan | top, nan | ubits(5), nan | top | ubits(9)], dtype=ubits).view(dt)
+        keys[rng.integers(0, n, max(1, n // 100))] = nans[rng.integers(0, 4, max(1, n // 100))]
+        keys[rng.integers(0, n, max(1, n // 100))] = np.array([tiny, -tiny, 3 * tiny, -3 * tiny], dtype=dt)[rng.integers(0, 4, max(1, n // 100))]
     elif dt.kind == "i":
         info = np.iinfo(dt)
         keys = rng.integers(info.min, info.max, n, dtype=dt, endpoint=True)
@@ -587,6 +596,8 @@ def test_typed_keys(G, bits, dtype, n):
     if dt.kind == "f":
         finite = gk[np.isfinite(gk)]
         assert (np.diff(finite) >= 0).all()
+        nan_below, nan_above = int((np.isnan(gk) & np.signbit(gk)).sum()), int((np.isnan(gk) & ~np.signbit(gk)).sum())
+        assert np.isnan(gk[:nan_below]).all() and np.isnan(gk[n - nan_above:]).all()  # NaNs beyond the infinities of their sign
     else:
         assert (np.diff(gk.astype(object) if dt.itemsize == 8 and dt.kind == "u" else gk.astype(np.float64)) >= 0).all()
     kb2 = G.ShaderStorageBuffer(keys)
