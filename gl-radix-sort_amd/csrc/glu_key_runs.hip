@@ -59,9 +59,9 @@ glu_status run(const Call& c)
 }
 } // namespace
 
-glu_status glu_hip::host::launch_tile_count_scan(uint32_t* tile_counts, uint32_t tiles, uint32_t* total, hipStream_t stream)
+glu_status glu_hip::host::launch_tile_count_scan(uint32_t* tile_counts, uint32_t tiles, uint32_t* total, hipStream_t stream, uint32_t most)
 {
-    hipLaunchKernelGGL(key_runs_scan_kernel, dim3(1), dim3(kSbThreads), 0, stream, tile_counts, tiles, total);
+    hipLaunchKernelGGL(key_runs_scan_kernel, dim3(1), dim3(kSbThreads), 0, stream, tile_counts, tiles, total, most);
     HIP_TRY(hipGetLastError());
     return GLU_OK;
 }

@@ -1,13 +1,22 @@
 // glu_merge.hip -- merge of libglu_hip.so (merge_kernels.hpp): glu_merge_create, glu_merge_destroy, glu_merge_prepare,
-// glu_merge_run_ptr, glu_merge_plan, glu_merge_last.
+// glu_merge_run_ptr, glu_merge_plan, glu_merge_last; and the set operations on merge's tiles (set_ops_kernels.hpp):
+// glu_set_ops_create, glu_set_ops_destroy, glu_set_ops_prepare, glu_set_ops_run_ptr, glu_set_ops_plan, glu_set_ops_last.
 // The library's other translation units: glu_host.hpp.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "glu_merge_object.hpp"
+#include "glu_set_ops_object.hpp"
 #include "merge_kernels.hpp"
+#include "set_ops_kernels.hpp"
 
 using namespace glu_hip;
 using namespace glu_hip::host;
+
+static_assert(GLU_SET_UNION == kSetUnion && GLU_SET_INTERSECTION == kSetIntersection && GLU_SET_DIFFERENCE == kSetDifference &&
+                  GLU_SET_SYMMETRIC_DIFFERENCE == kSetSymmetricDifference && GLU_SET_OP_COUNT_ == kSetOpCount,
+              "the header's operations are the kernels'");
 
 namespace
 {
@@ -49,6 +58,66 @@ glu_status run(glu_merge_s* s, const void* a_keys, const uint32_t* a_vals, size_
     m.tiles = p.tiles;
     m.split = (uint32_t*) s->split.ptr;
     return launch<K>(m, p, out_vals != nullptr, stream);
+}
+
+// ---- set operations
+glu_status check_set_total(size_t a_count, size_t b_count)
+{
+    if (a_count > kSetOpsMaxTotal || b_count > kSetOpsMaxTotal || (uint64_t) a_count + (uint64_t) b_count > kSetOpsMaxTotal)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "set operations take a_count + b_count below 2^32 (got %zu + %zu)", a_count, b_count);
+    return GLU_OK;
+}
+
+struct SetCall
+{
+    glu_set_ops_s* s;
+    int op;
+    const void *a_keys, *b_keys;
+    const uint32_t *a_vals, *b_vals;
+    size_t a_count, b_count;
+    void* out_keys;
+    uint32_t* out_vals;
+    size_t room; // min(max_out, the operation's bound); 0: the call only counts
+    uint32_t* num_out;
+    int key_type;
+    hipStream_t stream;
+};
+
+// Bounds, count, scan and (where something may be written) write.  The grids follow from the counts: never from the data.
+template<typename K>
+glu_status set_run(const SetCall& c, const SetOpsPlan& p, bool with_arrays)
+{
+    SetOpsArgs<K> m = {};
+    m.a_keys = (const K*) c.a_keys;
+    m.b_keys = (const K*) c.b_keys;
+    m.a_vals = c.a_vals;
+    m.b_vals = c.b_vals;
+    m.out_keys = (K*) c.out_keys;
+    m.out_vals = c.out_vals;
+    m.na = (uint32_t) c.a_count;
+    m.nb = (uint32_t) c.b_count;
+    m.xf = key_xf_of(c.key_type);
+    m.op = (uint32_t) c.op;
+    m.tiles = p.tiles;
+    m.room = (uint32_t) c.room;
+    m.bounds = (SetBounds*) c.s->scratch.ptr;
+    m.tile_counts = p.tiles ? (uint32_t*) (m.bounds + ((size_t) p.tiles + 1)) : nullptr;
+    const uint32_t most = set_ops_total(kSetOpsMaxTotal, set_op_bound(m.op, m.na, m.nb));
+    if (p.tiles)
+    {
+        hipLaunchKernelGGL((set_ops_bounds_kernel<K>), dim3(p.tiles / kMergeThreads + 1), dim3(kMergeThreads), 0, c.stream, m, p.tile);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL((set_ops_count_kernel<K>), dim3(p.tiles), dim3(kMergeThreads), 0, c.stream, m);
+        HIP_TRY(hipGetLastError());
+    }
+    GLU_TRY(launch_tile_count_scan(m.tile_counts, p.tiles, c.num_out, c.stream, most));
+    if (!p.tiles || !with_arrays) return GLU_OK;
+    if (c.out_vals)
+        hipLaunchKernelGGL((set_ops_write_kernel<K, true>), dim3(p.tiles), dim3(kMergeThreads), 0, c.stream, m);
+    else
+        hipLaunchKernelGGL((set_ops_write_kernel<K, false>), dim3(p.tiles), dim3(kMergeThreads), 0, c.stream, m);
+    HIP_TRY(hipGetLastError());
+    return GLU_OK;
 }
 } // namespace
 
@@ -125,6 +194,93 @@ glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels)
     GLU_TRY(check_not_null(merge, "merge"));
     store(tiles, merge->last.tiles);
     store(kernels, merge->last.kernels);
+    return GLU_OK;
+}
+
+
+// ---- set operations
+
+glu_status glu_set_ops_plan(size_t a_count, size_t b_count, glu_key_type key_type, int with_arrays, uint32_t* tile, uint32_t* tiles,
+                            uint32_t* kernels, size_t* scratch_bytes)
+{
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_set_total(a_count, b_count));
+    const SetOpsPlan p = set_ops_plan((uint64_t) a_count + b_count, key_bytes_of((int) key_type), with_arrays != 0);
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(kernels, p.kernels);
+    store(scratch_bytes, p.scratch_bytes);
+    return GLU_OK;
+}
+
+glu_status glu_set_ops_create(glu_set_ops* out) { return create_object(out); }
+
+glu_status glu_set_ops_destroy(glu_set_ops set_ops) { return destroy_object(set_ops); }
+
+glu_status glu_set_ops_prepare(glu_set_ops set_ops, size_t total_count, glu_key_type key_type)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(set_ops, "set_ops"));
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_set_total(total_count, 0));
+    return set_ops->scratch.reserve(set_ops_plan(total_count, key_bytes_of((int) key_type), true).scratch_bytes);
+}
+
+glu_status glu_set_ops_run_ptr(glu_set_ops set_ops, int op, const void* a_keys, const uint32_t* a_vals, size_t a_count, const void* b_keys,
+                               const uint32_t* b_vals, size_t b_count, void* out_keys, uint32_t* out_vals, size_t max_out, uint32_t* num_out,
+                               glu_key_type key_type, void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(set_ops, "set_ops"));
+    if (op < 0 || op >= GLU_SET_OP_COUNT_)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "op must be one of GLU_SET_UNION .. GLU_SET_SYMMETRIC_DIFFERENCE (got %d)", op);
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_set_total(a_count, b_count));
+    GLU_TRY(check_below_2_32(max_out, "max_out"));
+    const uint32_t kb = key_bytes_of((int) key_type);
+    const size_t total = a_count + b_count;
+    // a side of no elements is not looked at
+    if (!a_count) a_keys = nullptr, a_vals = nullptr;
+    if (!b_count) b_keys = nullptr, b_vals = nullptr;
+    if (a_count && !a_keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid a_keys buffer");
+    if (b_count && !b_keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid b_keys buffer");
+    if (!num_out) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid num_out pointer");
+    const bool with_arrays = out_keys != nullptr && max_out != 0; // (else the call only counts)
+    if (out_vals && !with_arrays)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "out_vals needs out_keys and max_out > 0 (a call that only counts takes neither)");
+    const bool with_vals = out_vals != nullptr;
+    if (a_count && (a_vals != nullptr) != with_vals)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "a_vals and out_vals must both be given or both be NULL");
+    // B's values are read exactly where its elements can be written
+    const bool b_written = with_vals && set_op_keeps_b((uint32_t) op) && b_count;
+    if (b_written && !b_vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "b_vals is required: the operation can write elements of B");
+    if (!b_written) b_vals = nullptr;
+    GLU_TRY(check_aligned(a_keys, kb, "a_keys", "the key size"));
+    GLU_TRY(check_aligned(b_keys, kb, "b_keys", "the key size"));
+    GLU_TRY(check_aligned(out_keys, kb, "out_keys", "the key size"));
+    GLU_TRY(check_aligned_4(a_vals, "a_vals"));
+    GLU_TRY(check_aligned_4(b_vals, "b_vals"));
+    GLU_TRY(check_aligned_4(out_vals, "out_vals"));
+    GLU_TRY(check_aligned_4(num_out, "num_out"));
+    // (no more than min(bound, max_out) entries of an output array can be written)
+    const size_t room = with_arrays ? (size_t) std::min<uint64_t>(set_op_bound((uint32_t) op, a_count, b_count), max_out) : 0;
+    GLU_TRY(check_disjoint({{out_keys, room * kb, "out_keys"}, {out_vals, room * 4, "out_vals"}, {num_out, sizeof(uint32_t), "num_out"}},
+                           {{a_keys, a_count * kb, "a_keys"}, {b_keys, b_count * kb, "b_keys"}, {a_vals, a_count * 4, "a_vals"}, {b_vals, b_count * 4, "b_vals"}},
+                           kOutputsAfterInputs));
+
+    const SetOpsPlan p = set_ops_plan(total, kb, with_arrays);
+    GLU_TRY(set_ops->scratch.reserve(p.scratch_bytes));
+    set_ops->last = {p.tiles, p.kernels};
+    const SetCall c{set_ops, op, a_keys, b_keys, a_vals, b_vals, a_count, b_count, out_keys, out_vals, room, num_out, (int) key_type, pick_stream(stream)};
+    return kb == 8 ? set_run<uint64_t>(c, p, with_arrays) : set_run<uint32_t>(c, p, with_arrays);
+}
+
+glu_status glu_set_ops_last(glu_set_ops set_ops, uint32_t* tiles, uint32_t* kernels)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(set_ops, "set_ops"));
+    store(tiles, set_ops->last.tiles);
+    store(kernels, set_ops->last.kernels);
     return GLU_OK;
 }
 

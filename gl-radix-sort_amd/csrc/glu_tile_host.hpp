@@ -25,7 +25,7 @@ struct TileCounts : Scratch
 inline uint32_t tile_grid(uint32_t tiles) { return std::max(1u, std::min(tiles, cus() * 8u)); }
 
 // The count scan, defined in glu_key_runs.hip (the one unit that holds key_runs_scan_kernel): one workgroup, enqueued on `stream`.
-// tile_counts[0 .. tiles) becomes its exclusive scan, *total (on the device) their sum.
-glu_status launch_tile_count_scan(uint32_t* tile_counts, uint32_t tiles, uint32_t* total, hipStream_t stream);
+// tile_counts[0 .. tiles) becomes its exclusive scan, *total (on the device) their sum, held to `most`.
+glu_status launch_tile_count_scan(uint32_t* tile_counts, uint32_t tiles, uint32_t* total, hipStream_t stream, uint32_t most = 0xFFFFFFFFu);
 } // namespace host
 } // namespace glu_hip

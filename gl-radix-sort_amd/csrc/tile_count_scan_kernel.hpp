@@ -7,9 +7,10 @@
 namespace glu_hip
 {
 // One workgroup.  tile_counts[0 .. tiles) becomes its exclusive scan by scan_batch_range -- the tile loop that scan_batch_block_kernel
-// runs over a long segment's partials, 4096 counts per round (kTileScanRound) with a running carry -- and *total their sum.
+// runs over a long segment's partials, 4096 counts per round (kTileScanRound) with a running carry -- and *total their sum, or
+// `most` if that is less (set operations on keys that are not sorted; everyone else passes 2^32 - 1).
 __global__ __launch_bounds__(kSbThreads) void key_runs_scan_kernel(uint32_t* __restrict__ tile_counts, uint32_t tiles,
-                                                                   uint32_t* __restrict__ total)
+                                                                   uint32_t* __restrict__ total, uint32_t most)
 {
     using T = Elem<uint32_t, 1>;
     __shared__ T wsum[2][kSbWaves];
@@ -19,7 +20,11 @@ __global__ __launch_bounds__(kSbThreads) void key_runs_scan_kernel(uint32_t* __r
     uint32_t phase = 0;
     scan_batch_range<uint32_t, 1>(reinterpret_cast<T*>(tile_counts), tiles, zero_elem<uint32_t, 1>(), threadIdx.x, wsum, phase);
     __syncthreads(); // (the last count's scan was stored by another thread of this workgroup)
-    if (threadIdx.x == 0) *total = tiles ? tile_counts[tiles - 1] + last : 0u;
+    if (threadIdx.x == 0)
+    {
+        const uint32_t sum = tiles ? tile_counts[tiles - 1] + last : 0u;
+        *total = sum < most ? sum : most;
+    }
 }
 
 } // namespace glu_hip

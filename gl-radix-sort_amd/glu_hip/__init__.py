@@ -132,6 +132,12 @@ SYMBOLS = [
     ("glu_merge_run_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
     ("glu_merge_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_merge_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_set_ops_create", _int, [_P(_vp)]),
+    ("glu_set_ops_destroy", _int, [_vp]),
+    ("glu_set_ops_prepare", _int, [_vp, _sz, _int]),
+    ("glu_set_ops_run_ptr", _int, [_vp, _int, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _int, _vp]),
+    ("glu_set_ops_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_set_ops_last", _int, [_vp, _P(_u32), _P(_u32)]),
     ("glu_histogram_create", _int, [_P(_vp)]),
     ("glu_histogram_destroy", _int, [_vp]),
     ("glu_histogram_prepare", _int, [_vp, _sz, _sz]),
@@ -385,6 +391,21 @@ def plan_merge(a_count, b_count, key_type="uint32", with_vals=True):
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_merge_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b),
                                ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+SetOp_Union, SetOp_Intersection, SetOp_Difference, SetOp_SymmetricDifference = 0, 1, 2, 3
+SET_OPS = {"union": SetOp_Union, "intersection": SetOp_Intersection, "difference": SetOp_Difference,
+           "symmetric_difference": SetOp_SymmetricDifference}
+
+
+def plan_set_ops(a_count, b_count, key_type="uint32", with_arrays=True):
+    """(tile, tiles, kernels, scratch_bytes) of a set operation on `a_count` and `b_count` keys (glu_set_ops_plan; host only): merge's
+    tile, ceil((a_count + b_count) / tile), 4 kernels (3 for a call that only counts, 1 for nothing), the bytes of the bounds and the
+    tile counts."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_set_ops_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_arrays else 0, ctypes.byref(a), ctypes.byref(b),
+                                 ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
 
 
@@ -764,6 +785,36 @@ class Merge(_Handle):
         """(tiles, kernels) of what the last run_ptr enqueued (glu_merge_last; no device read)."""
         a, b = _u32(), _u32()
         check(lib().glu_merge_last(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+
+class SetOps(_Handle):
+    """glu::SetOps (not in the reference) over the C ABI: union, intersection, difference and symmetric difference of two sorted
+    arrays of keys, with or without uint32 values, with std::set_* multiset semantics; the result and its length on the device."""
+
+    _CREATE, _DESTROY = "glu_set_ops_create", "glu_set_ops_destroy"
+
+    def __init__(self):
+        self._create()
+
+    def prepare(self, total_count, key_type="uint32"):
+        """Scratch for calls of up to `total_count` = a_count + b_count keys: they allocate nothing (capturable) (glu_set_ops_prepare)."""
+        check(lib().glu_set_ops_prepare(self._h, total_count, KEY_TYPES[key_type]))
+
+    def run_ptr(self, op, a_keys_ptr, a_vals_ptr, a_count, b_keys_ptr, b_vals_ptr, b_count, out_keys_ptr, out_vals_ptr, max_out,
+                num_out_ptr, key_type="uint32", stream=None):
+        """`op`: "union", "intersection", "difference" or "symmetric_difference" (or a SetOp_* constant).  The kept elements in merge's
+        order go to out[0 .. min(S, max_out)), their number S to *num_out (a uint32 on the device), also when S > max_out.  With
+        out_keys_ptr None or max_out 0 the call only counts.  Both inputs sorted in the sort's order and only read; all pointers are
+        device pointers (glu_set_ops_run_ptr)."""
+        check(lib().glu_set_ops_run_ptr(self._h, SET_OPS.get(op, op), _vp(a_keys_ptr), _vp(a_vals_ptr), a_count, _vp(b_keys_ptr),
+                                        _vp(b_vals_ptr), b_count, _vp(out_keys_ptr), _vp(out_vals_ptr), max_out, _vp(num_out_ptr),
+                                        KEY_TYPES[key_type], _vp(stream)))
+
+    def last(self):
+        """(tiles, kernels) of what the last run_ptr enqueued (glu_set_ops_last; no device read)."""
+        a, b = _u32(), _u32()
+        check(lib().glu_set_ops_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
 

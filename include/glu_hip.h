@@ -733,8 +733,8 @@ GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* pa
  *     output overlapping an input or the other output.  A refused call writes nothing.
  *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge
  *     an iota as the values, and fetch the wide values through the merged iota with glu_gather_run_ptr, the gather by an
- *     arbitrary permutation; it takes one source array, so A's and B's values are copied into one array first); set
- *     operations; a segmented merge; counts that live on the device. */
+ *     arbitrary permutation; it takes one source array, so A's and B's values are copied into one array first); a
+ *     segmented merge; counts that live on the device.  (Set operations on two sorted arrays: glu_set_ops_run_ptr below.) */
 typedef struct glu_merge_s* glu_merge;
 /* Not in the reference. */
 GLU_API glu_status glu_merge_create(glu_merge* out);
@@ -754,6 +754,78 @@ GLU_API glu_status glu_merge_plan(size_t a_count, size_t b_count, glu_key_type k
                                   uint32_t* kernels, size_t* scratch_bytes);
 /* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
 GLU_API glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels);
+
+/* ---- set operations (not in the reference): union, intersection, difference and symmetric difference of two sorted arrays of
+ * keys, with or without 4-byte values, on the device and on the caller's stream: std::set_union / set_intersection /
+ * set_difference / set_symmetric_difference, with their multiset semantics.  The result and its length stay on the device.
+ *   - ORDER AND EQUALITY are those of enc(key), enc being the encoding the sort gives a key (merge's order above).  Two keys are
+ *     equal iff their bits are: -0.0 and +0.0 are different keys, a NaN equals only the NaN with the same bits (the family's choice
+ *     for sort, merge, sorted search and top-k; not select's IEEE comparison).  Both inputs must be sorted in that order.
+ *   - For A[i] with key k: its rank among A's copies of k is rA(i) = i - lower_bound(A, k); B holds mB(k) = upper_bound(B, k) -
+ *     lower_bound(B, k) copies; A[i] is MATCHED iff rA(i) < mB(k).  B[j] is matched iff rB(j) < mA(k), the same the other way round.
+ *       GLU_SET_UNION                 every element of A, and the unmatched elements of B
+ *       GLU_SET_INTERSECTION          the matched elements of A (A's keys and values, never B's)
+ *       GLU_SET_DIFFERENCE            the unmatched elements of A
+ *       GLU_SET_SYMMETRIC_DIFFERENCE  the unmatched elements of A and the unmatched elements of B
+ *     A key m times in A and n times in B is max(m, n) / min(m, n) / max(m - n, 0) / |m - n| times in the output.  The output is the
+ *     kept elements in MERGE'S ORDER: A first among equal keys, each side in its own order.  Keys are copied bit for bit; values are
+ *     uint32_t and follow their keys.
+ *   - All six glu_key_type's.  a_count + b_count <= 2^32 - 1; max_out < 2^32.
+ *   - *num_out (uint32_t, on the device, required) always receives the number S of kept elements, also when S > max_out, and 0 when
+ *     both counts are 0.  out_keys[0 .. min(S, max_out)) and out_vals[0 .. min(S, max_out)) are written; entries behind them are not
+ *     touched (select's rule).  With out_keys NULL or max_out 0 the call ONLY COUNTS; out_vals must then be NULL too.
+ *   - VALUES: a_vals and out_vals are both NULL (keys only) or both non-NULL when a_count > 0.  b_vals is required exactly where
+ *     elements of B can be written: union or symmetric difference, with values, b_count > 0; intersection and difference ignore it
+ *     (it may be NULL).  A side of count 0 is not looked at: its pointers may be NULL.
+ *   - The inputs are READ ONLY.  With bound = the most outputs the operation can have -- a_count + b_count for union and symmetric
+ *     difference, a_count for difference, min(a_count, b_count) for intersection -- the first min(bound, max_out) entries of
+ *     out_keys and out_vals, and num_out, must not overlap any input range or each other (arrays that merely touch are fine).
+ *     Every array may start at any multiple of its element size.
+ *   - Four kernels when a_count + b_count > 0 (three when the call only counts), on merge's tiles: the bounds of every tile
+ *     boundary (merge's split, and where the copies of the first key behind it start in A and in B; 12 bytes a boundary of the
+ *     object's scratch), the kept elements of every tile counted in LDS, the counts scanned by one workgroup (which writes
+ *     *num_out), the kept elements of every tile written at their ranks by contiguous lanes.  With both counts 0 the scan alone
+ *     runs and writes 0.  No atomics, no look-back, no side stream, no host synchronisation, nothing in arrival order: the same
+ *     call gives the same bits every time.  No device allocation once glu_set_ops_prepare covered the total (else grow-only
+ *     allocation inside the call: not capturable).  The kernels and their grids follow from the counts and the addresses, never
+ *     from the data, so a captured call (one stream, no parallel branches) replays on any contents.
+ *   - An input that is NOT SORTED gives unspecified output contents and an unspecified *num_out <= bound; the call still never reads
+ *     or writes outside the arrays and writes nothing at or behind out[min(bound, max_out)].
+ *   - GLU_ERROR_INVALID_ARGUMENT for what the host can check, each with a message that names the argument: NULL set_ops; a NULL key
+ *     pointer of a side with elements; NULL num_out; a_vals without out_vals or the reverse; a required b_vals missing; out_vals in
+ *     a call that only counts; an op or a key type outside its list; misalignment; the limits above; an output overlapping an
+ *     input, another output or num_out.  A refused call writes nothing.
+ *   - OUT OF SCOPE: more than two inputs; set semantics that drop duplicates within one input (run glu_key_runs_run_ptr first: its
+ *     unique keys are a set); values wider than 4 bytes (carry an iota and gather, as for merge); the indices of the partners in B;
+ *     counts that live on the device. */
+typedef enum
+{
+    GLU_SET_UNION = 0,
+    GLU_SET_INTERSECTION = 1,
+    GLU_SET_DIFFERENCE = 2,
+    GLU_SET_SYMMETRIC_DIFFERENCE = 3,
+    GLU_SET_OP_COUNT_
+} glu_set_op;
+typedef struct glu_set_ops_s* glu_set_ops;
+/* Not in the reference. */
+GLU_API glu_status glu_set_ops_create(glu_set_ops* out);
+/* Not in the reference. */
+GLU_API glu_status glu_set_ops_destroy(glu_set_ops set_ops);
+/* Not in the reference.  Grow-only scratch (the bounds and the tile counts) for calls with a_count + b_count <= total_count keys of
+ * `key_type`: after it a call allocates nothing (and can be captured). */
+GLU_API glu_status glu_set_ops_prepare(glu_set_ops set_ops, size_t total_count, glu_key_type key_type);
+/* Not in the reference.  The contract above; `op` is a glu_set_op.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_set_ops_run_ptr(glu_set_ops set_ops, int op, const void* a_keys, const uint32_t* a_vals, size_t a_count,
+                                       const void* b_keys, const uint32_t* b_vals, size_t b_count, void* out_keys, uint32_t* out_vals,
+                                       size_t max_out, uint32_t* num_out, glu_key_type key_type, void* stream);
+/* Not in the reference.  Host only, no device, pure: tile = merge's (256 threads x 11 for 4-byte keys, x 7 for 8-byte keys), tiles =
+ * ceil((a_count + b_count) / tile), kernels = 4 with_arrays (out_keys given and max_out > 0), 3 for a call that only counts, 1 (the
+ * scan, which writes *num_out = 0) if both counts are 0; scratch_bytes = (tiles + 1) * 12 + tiles * 4 (0 if both counts are 0): what
+ * prepare reserves.  Any pointer may be NULL. */
+GLU_API glu_status glu_set_ops_plan(size_t a_count, size_t b_count, glu_key_type key_type, int with_arrays, uint32_t* tile,
+                                    uint32_t* tiles, uint32_t* kernels, size_t* scratch_bytes);
+/* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
+GLU_API glu_status glu_set_ops_last(glu_set_ops set_ops, uint32_t* tiles, uint32_t* kernels);
 
 /* ---- histogram (not in the reference): how many samples fall into each bin, over even bins (numpy.histogram with a range,
  * torch.histc, torch.bincount) or over sorted bin edges (numpy.histogram with edges), on the device and on the caller's stream.
