@@ -230,12 +230,13 @@ template<typename KeyT>
 glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t count, uint32_t first_bit, uint32_t end_bit,
                      hipStream_t stream, uint32_t key_xf = KEY_XF_NONE)
 {
+    // 1. checks, and the whole sort in one workgroup
     if (count <= 1 || first_bit >= end_bit) return GLU_OK; // RadixSort.hpp:278-279
     if (count > 0xFFFF0000ull) return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu does not fit 32-bit indexing", count);
     if (((uintptr_t) keys % sizeof(KeyT)) != 0 || (vals && ((uintptr_t) vals % sizeof(uint32_t)) != 0))
         return fail(GLU_ERROR_INVALID_ARGUMENT, "key/value arrays must be aligned to their element size");
     GLU_TRY(sort_prepare(s, count, sizeof(KeyT), vals != nullptr)); // RadixSort.hpp:281 (no-op when prepared)
-    s->last_planned = false; // (what glu_radix_sort_read_plan / read_finish report is about THIS sort)
+    s->last_planned = false; // (what glu_radix_sort_read_plan / read_finish report is about THIS sort: step 4)
     s->last_finish_attempted = false;
     s->last_finish_long_ok = false;
 
@@ -251,154 +252,70 @@ glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
 
     KeyT* kbuf[2] = {keys, (KeyT*) s->keys.ptr};
     uint32_t* vbuf[2] = {vals, vals ? (uint32_t*) s->vals.ptr : nullptr};
-    int cur = 0;
     s->cur_kind = 0;
     s->cur_behind = false; // (a call that failed half-way must not leave the next one's profile marks switched off)
     s->cur_seq = 0;
     // large sorts: device-side pass plan (constant-digit passes are skipped, the arrays' roles follow on the device)
     const bool planned = count >= kPlanMinCount && !s->no_plan;
-    s->last_planned = planned;
-    // the passes: digit positions, key transforms (typed keys: encode on the first pass's loads, decode on the last
-    // pass's stores), and which passes share one count kernel (radix_pair_passes.hpp)
-    struct PassDesc
-    {
-        uint32_t shift, bits, xform;
-        int pair_role;
-    };
-    PassDesc passes[kPlanMaxPasses];
-    uint32_t num_passes = 0;
-    for (uint32_t shift = first_bit; shift < end_bit;)
-    {
-        uint32_t bits = std::min<uint32_t>(s->digit_bits, end_bit - shift);
-        if (sizeof(KeyT) == 8 && shift < 32 && shift + bits > 32) bits = 32 - shift; // a digit stays inside one key word
-        const uint32_t xform = (shift == first_bit ? key_xf : 0u) | (shift + bits >= end_bit ? key_xf << 2 : 0u);
-        if (num_passes == kPlanMaxPasses) return fail(GLU_ERROR_INVALID_ARGUMENT, "too many passes");
-        passes[num_passes++] = PassDesc{shift, bits, xform, 0};
-        shift += bits;
-    }
-    // A leader is a pass of the line kernel that does not encode keys on load; its follower is the pass after it, of the
-    // line kernel of the same digit width (wider than 4 bits: the 8-bit kernels, else the 4-bit ones).
     const bool pair_tables = planned && s->pairs && s->pair_t2.ptr;
     const bool pairs_ok = pair_tables && count >= (s->pair_min ? s->pair_min : kPairMinKeyBytes / sizeof(KeyT));
-    // Whole keys, 8-bit digits, line passes, from finish_min_count elements: the sort first tries to end in LDS
-    // (radix_lds_finish.hpp) -- the two top-bit passes and the in-LDS pass are enqueued in front of the ordinary passes, and the
-    // device runs one of the two sequences.
+    const bool lines8 = lines_applicable<KeyT, 8>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count);
+    const bool lines4 = lines_applicable<KeyT, 4>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count);
+
+    // 2. the attempt.  Whole keys, 8-bit digits (one pass per key byte), line passes, from finish_min_count elements: the sort first
+    // tries to end in LDS (radix_lds_finish.hpp) -- the two top-bit passes and the in-LDS pass are enqueued in front of the ordinary
+    // passes, and the device runs one of the two sequences.
     uint32_t finish_kpt = 0; // (the geometry that suits uniform keys; 0: no attempt)
-    uint32_t finish_top_bit = end_bit;
-    if (pair_tables && s->lds_finish && s->finish_starts.ptr && first_bit == 0 &&
-        end_bit == 8 * sizeof(KeyT) && s->digit_bits == 8 && num_passes == sizeof(KeyT) && count >= (s->finish_min ? s->finish_min : finish_min_count(sizeof(KeyT))) &&
-        lines_applicable<KeyT, 8>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count))
+    if (pair_tables && s->lds_finish && s->finish_starts.ptr && first_bit == 0 && end_bit == 8 * sizeof(KeyT) && s->digit_bits == 8 &&
+        count >= (s->finish_min ? s->finish_min : finish_min_count(sizeof(KeyT))) && lines8)
         finish_kpt = finish_geometry_for(count);
-    // The runs' key bits are chosen on the device from a sample of the keys (untyped keys: radix_sample_top_kernel); the host only
-    // remembers, as a floor for the next sample, the exact top bit of an attempt that was refused because its sample had missed
-    // a varying bit.  GLU_HIP_SORT_DEVICE_TOP=0: the host guesses from the object's last attempt (round 4, below).
+    // The runs' key bits are chosen on the device from a sample of the keys (untyped keys: radix_sample_top_kernel).
+    // GLU_HIP_SORT_DEVICE_TOP=0: the host guesses from the object's last attempt (sort_call_plan.hpp: finish_attempts has both rules).
     const bool device_top = finish_kpt && s->device_top && key_xf == KEY_XF_NONE && !s->no_bit_shortcut;
-    if (finish_kpt && s->finish_hint && device_top)
-    {
-        const uint32_t seen = s->finish_seq ? __atomic_load_n(s->finish_hint, __ATOMIC_ACQUIRE) : 0u;
-        if (s->finish_wait == 0 && s->finish_seq && (seen >> 3) == s->finish_seq) // the last attempt's outcome has arrived
-        {
-            if (seen & 7u) s->finish_last_geo = seen & 7u; // the tile it took
-            s->finish_last_refused = (seen & 7u) == 0u;
-            if (s->finish_seq != s->finish_seq_acted_on)    // (acted on once)
-            {
-                s->finish_seq_acted_on = s->finish_seq;
-                bool range_miss = false;
-                if (__atomic_load_n(s->finish_hint + 3, __ATOMIC_ACQUIRE) == s->finish_seq)
-                {
-                    const uint64_t varying = (uint64_t) s->finish_hint[1] | ((uint64_t) s->finish_hint[2] << 32);
-                    const uint32_t exact = varying ? 64u - (uint32_t) __builtin_clzll(varying) : 0u, used = s->finish_hint[4];
-                    range_miss = !(seen & 7u) && exact > used;
-                    if (range_miss)
-                        s->top_floor = exact; // the sample missed a bit that varies: the next one starts from here
-                    else if (exact < s->top_floor)
-                        s->top_floor = 0;     // (other keys now)
-                }
-                if (!(seen & 7u) && !range_miss && s->finish_backoff) s->finish_wait = s->finish_backoff; // refused for its runs: do not ask again for a while
-            }
-        }
-        if (s->finish_wait)
-        {
-            s->finish_wait--;
-            finish_kpt = 0;
-        }
-    }
-    else if (finish_kpt && s->finish_hint)
-    {
-        const uint32_t seen = s->finish_seq ? __atomic_load_n(s->finish_hint, __ATOMIC_ACQUIRE) : 0u;
-        if (s->finish_wait == 0 && s->finish_seq && (seen >> 3) == s->finish_seq) // the last attempt's outcome has arrived
-        {
-            if (seen & 7u) s->finish_last_geo = seen & 7u; // the tile it took
-            s->finish_last_refused = (seen & 7u) == 0u;
-            if (s->finish_seq != s->finish_seq_acted_on)    // (acted on once)
-            {
-                s->finish_seq_acted_on = s->finish_seq;
-                const uint32_t was = s->finish_top ? s->finish_top : end_bit;
-                uint32_t top = was;
-                if (__atomic_load_n(s->finish_hint + 3, __ATOMIC_ACQUIRE) == s->finish_seq)
-                {
-                    // which key bits varied: the runs of the next attempt are the values of the top 16 of those
-                    const uint64_t varying = (uint64_t) s->finish_hint[1] | ((uint64_t) s->finish_hint[2] << 32);
-                    top = varying ? 64u - (uint32_t) __builtin_clzll(varying) : 16u;
-                    top = std::min<uint32_t>(std::max<uint32_t>(top, 16u), end_bit);
-                    if (sizeof(KeyT) == 8 && top > 32 && top < 48 && top != 40) top = top < 40 ? 40 : 48; // a digit stays inside one key word
-                }
-                if (top != was)
-                    s->finish_top = top; // the assumption changes: what the last attempt was told says nothing about the next
-                else if (!(seen & 7u) && s->finish_backoff)
-                    s->finish_wait = s->finish_backoff; // refused under the same assumption: do not ask again for a while
-            }
-        }
-        if (s->finish_wait)
-        {
-            s->finish_wait--;
-            finish_kpt = 0;
-        }
-    }
     if (finish_kpt)
     {
-        s->finish_seq = s->finish_seq >= 0x0FFFFFFFu ? 1u : s->finish_seq + 1;
-        s->cur_seq = s->finish_seq;
-        for (uint32_t i = num_passes; i-- > 0;) passes[i + 2] = passes[i];
-        // (typed keys and sorts that do not collect which bits vary: the whole key's top bits)
-        finish_top_bit = !device_top && key_xf == KEY_XF_NONE && !s->no_bit_shortcut && s->finish_top ? std::min<uint32_t>(s->finish_top, end_bit) : end_bit;
-        passes[0] = PassDesc{finish_top_bit - 16u, 8u, key_xf, 0}; // (typed keys: encoded on load here, decoded on store by the in-LDS pass)
-        passes[1] = PassDesc{finish_top_bit - 8u, 8u, 0u, 0};
-        num_passes += 2;
+        uint32_t hint[5] = {};
+        if (s->finish_hint) // (word 0 was stored last: what is read behind it belongs to that attempt or a later one)
+        {
+            hint[0] = __atomic_load_n(s->finish_hint, __ATOMIC_ACQUIRE);
+            hint[3] = __atomic_load_n(s->finish_hint + 3, __ATOMIC_ACQUIRE);
+            hint[1] = s->finish_hint[1], hint[2] = s->finish_hint[2], hint[4] = s->finish_hint[4];
+        }
+        if (!finish_attempts(s->feedback, s->finish_hint ? hint : nullptr, device_top, sizeof(KeyT), end_bit)) finish_kpt = 0;
     }
+    if (finish_kpt) s->cur_seq = s->feedback.finish_seq;
+    // (typed keys and sorts that do not collect which bits vary: the whole key's top bits)
+    const uint32_t finish_top_bit = finish_kpt && !device_top && key_xf == KEY_XF_NONE && !s->no_bit_shortcut && s->feedback.finish_top
+                                        ? std::min<uint32_t>(s->feedback.finish_top, end_bit)
+                                        : end_bit;
     // runs longer than the tile: segmented passes over just them (4-byte untyped keys with values, all 16 low bits inside two digits)
     // (every key type since round 6; the passes cover 16 low bits of 4-byte keys, 48 of 8-byte keys)
     const bool finish_long_ok = finish_kpt && s->long_runs && s->long_image.ptr && finish_top_bit >= 16 &&
                                 finish_top_bit - 16u <= (sizeof(KeyT) == 4 ? 16u : 48u);
+    const uint32_t finish_last = std::min<uint32_t>(finish_kpt + 2, kFinishGeometries); // the larger tiles enqueued behind it
+    // the one that gets a workgroup per run: what this object's last sort took if that is among them, else the uniform-keys one
+    const uint32_t finish_expected =
+        s->feedback.finish_last_geo >= finish_kpt && s->feedback.finish_last_geo <= finish_last ? s->feedback.finish_last_geo : finish_kpt;
+
+    // 3. the passes (sort_call_plan.hpp)
+    static_assert(kSortCallMaxPasses == (uint32_t) kPlanMaxPasses, "a call's pass list is as long as the device-side plan");
+    SortPassList list;
+    if (!sort_call_passes(list, sizeof(KeyT), first_bit, end_bit, s->digit_bits, key_xf, finish_kpt != 0, finish_top_bit, pairs_ok, lines8, lines4))
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "too many passes");
+    const SortPass* const passes = list.passes;
+    const uint32_t num_passes = list.num;
+
+    // 4. what the read_* entry points report about this sort
+    s->last_planned = planned;
+    s->last_finish_attempted = finish_kpt != 0;
     s->last_finish_long_ok = finish_long_ok;
     s->last_device_top = finish_kpt && device_top;
     s->last_finish_top = finish_kpt ? finish_top_bit : 0u;
-    s->last_finish_attempted = finish_kpt != 0;
-    const uint32_t finish_last = std::min<uint32_t>(finish_kpt + 2, kFinishGeometries); // the larger tiles enqueued behind it
-    // the one that gets a workgroup per run: what this object's last sort took if that is among them, else the uniform-keys one
-    const uint32_t finish_expected = s->finish_last_geo >= finish_kpt && s->finish_last_geo <= finish_last ? s->finish_last_geo : finish_kpt;
     s->last_finish_capacity = finish_kpt ? finish_geometry_capacity(finish_last) : 0u;
-    if (pairs_ok || finish_kpt)
-    {
-        const bool lines8 = lines_applicable<KeyT, 8>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count);
-        const bool lines4 = lines_applicable<KeyT, 4>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count);
-        for (uint32_t i = 0; i + 1 < num_passes;)
-        {
-            const bool wide = passes[i].bits > 4;
-            // (below the size from which ordinary passes pair, only the two top-bit passes of an attempt to end in LDS do)
-            // (a leader does not encode keys on load -- except the first top-bit pass of an attempt, whose 8-bit pair-count
-            // kernel has the encoding instantiation)
-            if ((pairs_ok || (finish_kpt && i == 0)) && wide == (passes[i + 1].bits > 4) && (wide ? lines8 : lines4) &&
-                ((passes[i].xform & 3u) == 0 || (finish_kpt && i == 0)))
-            {
-                passes[i].pair_role = 1;
-                passes[i + 1].pair_role = 2;
-                i += 2;
-            }
-            else
-                i += 1;
-        }
-    }
+    if (planned)
+        for (uint32_t i = 0; i < kSortCallMaxPasses; i++) s->last_pair_roles[i] = i < num_passes ? (uint32_t) passes[i].pair_role : 0u;
+
+    // 5. enqueue
     if (planned)
     {
         // per sort: no follower counts for itself yet, nothing is known about the key bits
@@ -410,17 +327,31 @@ glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
         if (finish_kpt && device_top)
         {
             hipLaunchKernelGGL((radix_sample_top_kernel<KeyT>), dim3(kSampleTopBlocks), dim3(256), 0, stream, (const KeyT*) kbuf[0], (uint32_t) count, end_bit,
-                               std::min<uint32_t>(s->top_floor, end_bit), plan);
+                               std::min<uint32_t>(s->feedback.top_floor, end_bit), plan);
             HIP_TRY(hipGetLastError());
         }
     }
-    if (planned)
-        for (uint32_t i = 0; i < (uint32_t) kPlanMaxPasses; i++) s->last_pair_roles[i] = i < num_passes ? (uint32_t) passes[i].pair_role : 0u;
     // (see glu_radix_sort_s::side)
     // Four cross-stream dependencies cost 0.1 ms that only long kernels hide: a sort whose attempt is refused and whose
     // ordinary passes skip (2^28 all-zero keys, the reference's benchmark input: 0.22 ms on one queue, 0.35 forked) is
     // better off on one queue -- so an object whose last known attempt was refused does not fork (the first sort of an object does).
-    const bool fork = planned && finish_kpt && s->fork_behind && !s->finish_last_refused && s->ensure_side();
+    const bool fork = planned && finish_kpt && s->fork_behind && !s->feedback.finish_last_refused && s->ensure_side();
+    // Once the side stream has forked (behind the plan kernel of pass 0: launch_pass_lines) it joins the caller's queue on every way
+    // out of this function: no kernel stays in flight on a stream the caller cannot wait for, no capture ends with an unjoined fork.
+    // The destructor is the way out of a failure and ignores what the two calls return.
+    struct SideJoin
+    {
+        glu_radix_sort_s* s;
+        hipStream_t stream;
+        hipError_t join()
+        {
+            s->side_forked = false;
+            const hipError_t e = hipEventRecord(s->ev_join, s->side);
+            return e != hipSuccess ? e : hipStreamWaitEvent(stream, s->ev_join, 0);
+        }
+        ~SideJoin() { if (s->side_forked) (void) join(); }
+    } side_join{s, stream};
+    int cur = 0; // (sorts without a plan: which pair of arrays holds the data)
     uint32_t pass = 0;
     for (; pass < num_passes; pass++)
     {
@@ -449,7 +380,7 @@ glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
                 pa.finish_geo_last = finish_last;
                 pa.finish_first_ordinary = 2;
                 pa.finish_num_ordinary = num_passes - 2;
-                pa.finish_seq = s->finish_seq;
+                pa.finish_seq = s->feedback.finish_seq;
                 pa.finish_top_bit = finish_top_bit;
                 pa.finish_key_bits = end_bit;
                 pa.finish_long_ok = finish_long_ok;
@@ -458,36 +389,23 @@ glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
             pa.unitsum_side = fork && pass == 1 && pa.pair_role == 2 && bits == 8;
             GLU_TRY(dispatch_pass<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, shift, bits, nullptr,
                                         fork && pa.behind_attempt ? s->side : stream, xform, pa));
+            if (finish_kpt && pass == 1)
             {
-                if (finish_kpt && pass == 1)
-                {
-                    if (fork) HIP_TRY(hipEventRecord(s->ev_fork2, stream)); // (the data is where the in-LDS pass and the long-run passes find it)
-                    // the in-LDS pass, in place on whichever pair of arrays holds the data now (returns at once if the
-                    // device chose the ordinary passes, which follow)
-                    s->cur_kind = 2;
-                    s->cur_behind = false;
-                    s->mark(stream);
-                    s->mark(stream);
-                    const FinishMarks finish_marks{[](void* object, hipStream_t st) { ((glu_radix_sort_s*) object)->mark(st, true); }, s};
-#define GLU_LAUNCH_FINISH(VALS_, XF_)                                                                                             \
-    GLU_TRY((launch_finish<KeyT, VALS_, XF_>(kbuf[0], VALS_ ? vbuf[0] : nullptr, kbuf[1], VALS_ ? vbuf[1] : nullptr,              \
-                                             (const uint32_t*) s->finish_starts.ptr, finish_kpt, finish_last, finish_expected,    \
-                                             finish_top_bit - 16u, pa.plan, 2u, key_xf, stream, s->finish_rank_bits,              \
-                                             (uint32_t*) s->finish_crowded.ptr, finish_marks)))
-                    if (vals)
-                    {
-                        if (key_xf != KEY_XF_NONE) GLU_LAUNCH_FINISH(true, true);
-                        else GLU_LAUNCH_FINISH(true, false);
-                    }
-                    else
-                    {
-                        if (key_xf != KEY_XF_NONE) GLU_LAUNCH_FINISH(false, true);
-                        else GLU_LAUNCH_FINISH(false, false);
-                    }
-#undef GLU_LAUNCH_FINISH
-                    if (finish_long_ok && !fork)
-                        GLU_TRY(launch_long_run_passes_any<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, key_xf, stream));
-                }
+                if (fork) HIP_TRY(hipEventRecord(s->ev_fork2, stream)); // (the data is where the in-LDS pass and the long-run passes find it)
+                // the in-LDS pass, in place on whichever pair of arrays holds the data now (returns at once if the
+                // device chose the ordinary passes, which follow)
+                s->cur_kind = 2;
+                s->cur_behind = false;
+                s->mark(stream);
+                s->mark(stream);
+                const FinishMarks finish_marks{[](void* object, hipStream_t st) { ((glu_radix_sort_s*) object)->mark(st, true); }, s};
+                // (keys-only sorts: vbuf[] holds null pointers)
+                const auto finish = vals ? (key_xf != KEY_XF_NONE ? launch_finish<KeyT, true, true> : launch_finish<KeyT, true, false>)
+                                         : (key_xf != KEY_XF_NONE ? launch_finish<KeyT, false, true> : launch_finish<KeyT, false, false>);
+                GLU_TRY(finish(kbuf[0], vbuf[0], kbuf[1], vbuf[1], (const uint32_t*) s->finish_starts.ptr, finish_kpt, finish_last, finish_expected,
+                               finish_top_bit - 16u, pa.plan, 2u, key_xf, stream, s->finish_rank_bits, (uint32_t*) s->finish_crowded.ptr, finish_marks));
+                if (finish_long_ok && !fork)
+                    GLU_TRY(launch_long_run_passes_any<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, key_xf, stream));
             }
         }
         else
@@ -503,20 +421,15 @@ glu_status sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t cou
         // the side stream: (behind the ordinary passes) the segmented passes over long runs, beside the in-LDS pass; then it joins
         HIP_TRY(hipStreamWaitEvent(s->side, s->ev_fork2, 0));
         if (finish_long_ok) GLU_TRY(launch_long_run_passes_any<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, key_xf, s->side));
-        HIP_TRY(hipEventRecord(s->ev_join, s->side));
-        HIP_TRY(hipStreamWaitEvent(stream, s->ev_join, 0));
+        HIP_TRY(side_join.join());
     }
     if (planned)
     {
         // the data is home unless an odd number of passes ran: decided and, if need be, copied on the device
         const dim3 grid((uint32_t) std::min<size_t>((count + 255) / 256, (size_t) g_dev.num_cus * 16));
-        if (vals)
-            hipLaunchKernelGGL((radix_finalize_kernel<KeyT, true>), grid, dim3(256), 0, stream, kbuf[0], vbuf[0], (const KeyT*) kbuf[1],
-                               (const uint32_t*) vbuf[1], (uint32_t) count, (const PassPlan*) s->plan.ptr, pass, finish_kpt ? 2u : 0u);
-        else
-            hipLaunchKernelGGL((radix_finalize_kernel<KeyT, false>), grid, dim3(256), 0, stream, kbuf[0], (uint32_t*) nullptr,
-                               (const KeyT*) kbuf[1], (const uint32_t*) nullptr, (uint32_t) count, (const PassPlan*) s->plan.ptr, pass,
-                               finish_kpt ? 2u : 0u);
+        const auto finalize = vals ? radix_finalize_kernel<KeyT, true> : radix_finalize_kernel<KeyT, false>;
+        hipLaunchKernelGGL(finalize, grid, dim3(256), 0, stream, kbuf[0], vbuf[0], (const KeyT*) kbuf[1], (const uint32_t*) vbuf[1],
+                           (uint32_t) count, (const PassPlan*) s->plan.ptr, pass, finish_kpt ? 2u : 0u);
         HIP_TRY(hipGetLastError());
         return GLU_OK;
     }
@@ -561,10 +474,34 @@ __global__ void tune_fill_kernel(uint32_t* __restrict__ p, size_t words, uint32_
     }
 }
 
-glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_size)
+// What the two callers of the search differ in (the fourth difference, what happens when nothing was chosen, is theirs).
+struct PlacementSearch
 {
-    // (grow-only: an array that is already larger than this count needs keeps its size)
-    const size_t kbytes = std::max(count * key_size, s->keys.size), vbytes = std::max(count * sizeof(uint32_t), s->vals.size);
+    const char *what, *candidate; // the words of the log lines
+    // Where the chosen pair goes, and which pair the candidates are.  The object's own scratch: every candidate stands in as the
+    // scratch while copies of a caller's side are sorted.  Other arrays: every candidate is sorted itself, against the scratch in place.
+    Scratch *keys, *vals;
+    size_t kbytes, vbytes; // (what the two arrays are allocated with)
+    size_t count, key_size; // the calibration sort
+    const char* list; // GLU_HIP_SCRATCH_TUNE_LIST, or nullptr: it does not apply
+};
+struct Placement
+{
+    bool found = false;           // a pair was chosen and is in place; else the arrays are empty
+    bool short_of_memory = false; // no search: free_mib < want_mib
+    size_t free_mib = 0, want_mib = 0;
+    uint32_t spacer_mib = 0, tried = 0;
+    double ms = 0, worst_ms = 0;
+};
+
+// The search: allocate keys, a spacer and values, free the spacer, fill, sort three times and time two of them, keep the fastest
+// pair.  Leaves profiling, tuning and last_planned as a caller's sort expects them on every way out, and the best pair so far (if
+// any) in place even when it fails.
+glu_status search_placement(glu_radix_sort_s* s, const PlacementSearch& how, Placement& out)
+{
+    out = Placement();
+    const bool own_scratch = how.keys == &s->keys;
+    const size_t kbytes = how.kbytes, vbytes = how.vbytes;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GLU_OK;
     // up to 16 candidates, the value array behind spacers of 0, 0.5 .. 7.5 GiB (which spacer wins differs from process to
@@ -575,91 +512,75 @@ glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_
     // 15.5 GiB).  GLU_HIP_SCRATCH_TUNE_LIST=step_mib:count[:first_mib] fixes the list (no early end).
     size_t step_mib = 512, candidates = 16, first_mib = 0;
     const auto t_begin = std::chrono::steady_clock::now();
-    const char* const tune_list = glu_env("GLU_HIP_SCRATCH_TUNE_LIST");
-    const bool fixed_list = tune_list != nullptr;
-    if (const char* e = tune_list) sscanf(e, "%zu:%zu:%zu", &step_mib, &candidates, &first_mib);
+    const bool fixed_list = how.list != nullptr;
+    if (how.list) sscanf(how.list, "%zu:%zu:%zu", &step_mib, &candidates, &first_mib);
     std::vector<size_t> spacers_mib;
     for (size_t i = 0; i < std::max<size_t>(candidates, 1); i++) spacers_mib.push_back(first_mib + i * step_mib);
-    // room for the caller-side copies, one candidate with its spacer and the best so far (twice over, to be safe)
-    const size_t need_b = 2 * (2 * (kbytes + vbytes) + (spacers_mib.back() << 20)) + ((size_t) 1 << 30);
-    s->tuned_candidates = 0, s->tuned_ms = s->tuned_worst_ms = 0.0, s->tuned_spacer_mib = 0;
+    // room for one candidate with its spacer and the best so far, and for the caller-side copies (twice over, to be safe)
+    const size_t need_b = 2 * ((own_scratch ? 2 : 1) * (kbytes + vbytes) + (spacers_mib.back() << 20)) + ((size_t) 1 << 30);
     if (free_b < need_b)
     {
-        if (glu_verbose())
-            fprintf(stderr, "[glu_hip] scratch placement skipped: %zu MiB free, the search wants %zu MiB; plain allocation\n", free_b >> 20,
-                    need_b >> 20);
+        out.short_of_memory = true, out.free_mib = free_b >> 20, out.want_mib = need_b >> 20;
         return GLU_OK;
     }
     // the calibration sorts run on the library queue and rewrite this object's tables: nothing of the caller's may still be
     // using them on another stream
-    if (hipDeviceSynchronize() != hipSuccess) return fail(GLU_ERROR_DEVICE, "hipDeviceSynchronize failed before the scratch placement");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(GLU_ERROR_DEVICE, "hipDeviceSynchronize failed before the %s placement", how.what);
     hipStream_t st = g_dev.queue;
-    void *a = nullptr, *b = nullptr;
+    void *a = nullptr, *b = nullptr; // (own_scratch) the caller's side of the calibration sorts
     hipEvent_t e0 = nullptr, e1 = nullptr;
     struct Cand { void* k = nullptr; void* v = nullptr; double ms = 1e30; uint32_t spacer = 0; } best;
     double worst = 0;
     uint32_t tried = 0;
-    s->tuning = true;
+    s->tuning = true; // (the sorts below must not start a search of their own)
     const int was_profiling = s->profiling;
     s->profiling = 0; // the calibration sorts are not the caller's
-    s->keys.release();
-    s->vals.release();
-    auto cleanup = [&](glu_status status) {
+    how.keys->release();
+    how.vals->release();
+    auto done = [&](glu_status status) {
         s->profiling = was_profiling;
         (void) hipStreamSynchronize(st);
         if (a) (void) hipFree(a);
         if (b) (void) hipFree(b);
         if (e0) (void) hipEventDestroy(e0);
         if (e1) (void) hipEventDestroy(e1);
-        s->keys.ptr = best.k, s->keys.size = best.k ? kbytes : 0;
-        s->vals.ptr = best.v, s->vals.size = best.v ? vbytes : 0;
+        how.keys->ptr = best.k, how.keys->size = best.k ? kbytes : 0;
+        how.vals->ptr = best.v, how.vals->size = best.v ? vbytes : 0;
         s->tuning = false;
         s->last_planned = false; // glu_radix_sort_read_plan: the calibration sorts were not the caller's
+        if (best.k) out.found = true, out.spacer_mib = best.spacer, out.tried = tried, out.ms = best.ms, out.worst_ms = worst;
         return status;
     };
-#define TUNE_TRY(expr)                                                                                                 \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return cleanup(fail(GLU_ERROR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)));   \
-    } while (0)
-    TUNE_TRY(hipMalloc(&a, kbytes));
-    TUNE_TRY(hipMalloc(&b, vbytes));
-    TUNE_TRY(hipEventCreate(&e0));
-    TUNE_TRY(hipEventCreate(&e1));
+    hipError_t err = own_scratch ? hipMalloc(&a, kbytes) : hipSuccess;
+    if (err == hipSuccess && own_scratch) err = hipMalloc(&b, vbytes);
+    if (err == hipSuccess) err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    if (err != hipSuccess) return done(fail(GLU_ERROR_DEVICE, "the %s placement could not start: %s", how.what, hipGetErrorString(err)));
     for (size_t spacer_mib : spacers_mib)
     {
         void *k = nullptr, *sp = nullptr, *v = nullptr;
-        if (hipMalloc(&k, kbytes) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            break; // out of memory: the best so far (or the plain allocation of sort_prepare, which reports the failure)
-        }
-        if (spacer_mib && hipMalloc(&sp, spacer_mib << 20) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            (void) hipFree(k);
-            continue;
-        }
-        if (hipMalloc(&v, vbytes) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            (void) hipFree(k);
-            if (sp) (void) hipFree(sp);
-            continue;
-        }
+        const bool got = hipMalloc(&k, kbytes) == hipSuccess && (!spacer_mib || hipMalloc(&sp, spacer_mib << 20) == hipSuccess) &&
+                         hipMalloc(&v, vbytes) == hipSuccess;
         if (sp) (void) hipFree(sp); // the arrays stay where they are
-        s->keys.ptr = k, s->keys.size = kbytes;
-        s->vals.ptr = v, s->vals.size = vbytes;
+        if (!got)
+        {
+            (void) hipGetLastError();
+            if (!k) break; // out of memory: the best so far (or the caller's plain allocation, which reports the failure)
+            (void) hipFree(k); // (no room for this spacer or for the values behind it: the next one)
+            continue;
+        }
+        if (own_scratch) s->keys.ptr = k, s->keys.size = kbytes, s->vals.ptr = v, s->vals.size = vbytes;
+        void* const sort_k = own_scratch ? a : k;
+        void* const sort_v = own_scratch ? b : v;
         double ms = 1e30;
         glu_status status = GLU_OK;
         for (int rep = 0; rep < 3 && status == GLU_OK; rep++) // the first run is a warm-up
         {
-            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) a, kbytes / 4, 0x5EEDu + rep);
-            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) b, vbytes / 4, 77u);
+            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) sort_k, kbytes / 4, 0x5EEDu + rep);
+            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) sort_v, vbytes / 4, 77u);
             (void) hipEventRecord(e0, st);
-            status = key_size == 8 ? sort_run<uint64_t>(s, (uint64_t*) a, (uint32_t*) b, count, 0, st)
-                                   : sort_run<uint32_t>(s, (uint32_t*) a, (uint32_t*) b, count, 0, st);
+            status = how.key_size == 8 ? sort_run<uint64_t>(s, (uint64_t*) sort_k, (uint32_t*) sort_v, how.count, 0, st)
+                                       : sort_run<uint32_t>(s, (uint32_t*) sort_k, (uint32_t*) sort_v, how.count, 0, st);
             (void) hipEventRecord(e1, st);
             if (status == GLU_OK && hipEventSynchronize(e1) == hipSuccess && rep > 0)
             {
@@ -667,17 +588,16 @@ glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_
                 if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms = std::min(ms, (double) t);
             }
         }
-        s->keys.ptr = nullptr, s->keys.size = 0;
-        s->vals.ptr = nullptr, s->vals.size = 0;
+        if (own_scratch) s->keys.ptr = nullptr, s->keys.size = 0, s->vals.ptr = nullptr, s->vals.size = 0;
+        (void) hipStreamSynchronize(st);
         if (status != GLU_OK)
         {
-            (void) hipStreamSynchronize(st);
             (void) hipFree(k);
             (void) hipFree(v);
-            return cleanup(status);
+            return done(status);
         }
         if (ms < 1e29) worst = std::max(worst, ms);
-        if (glu_verbose()) fprintf(stderr, "[glu_hip]   candidate: keys %p values %p (spacer %zu MiB): %.3f ms\n", k, v, spacer_mib, ms);
+        if (glu_verbose()) fprintf(stderr, "[glu_hip]   %s: keys %p values %p (spacer %zu MiB): %.3f ms\n", how.candidate, k, v, spacer_mib, ms);
         if (ms < best.ms)
         {
             if (best.k) (void) hipFree(best.k);
@@ -693,15 +613,24 @@ glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_
         if (!fixed_list && tried >= 8 && best.ms <= 0.93 * worst) break;
         if (!fixed_list && std::chrono::steady_clock::now() - t_begin > std::chrono::milliseconds(1000)) break;
     }
-#undef TUNE_TRY
-    s->tuned_spacer_mib = best.spacer;
-    s->tuned_ms = best.k ? best.ms : 0.0;
-    s->tuned_worst_ms = best.k ? worst : 0.0;
-    s->tuned_candidates = best.k ? tried : 0u;
-    if (glu_verbose())
+    return done(GLU_OK);
+}
+
+// The object's own scratch (sort_prepare).  Nothing chosen: sort_prepare's plain allocation follows, and reports zero candidates.
+glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_size)
+{
+    // (grow-only: an array that is already larger than this count needs keeps its size)
+    const PlacementSearch how{"scratch", "candidate", &s->keys, &s->vals, std::max(count * key_size, s->keys.size),
+                              std::max(count * sizeof(uint32_t), s->vals.size), count, key_size, glu_env("GLU_HIP_SCRATCH_TUNE_LIST")};
+    Placement p;
+    GLU_TRY(search_placement(s, how, p));
+    s->tuned_spacer_mib = p.spacer_mib, s->tuned_candidates = p.tried, s->tuned_ms = p.ms, s->tuned_worst_ms = p.worst_ms;
+    if (glu_verbose() && p.short_of_memory)
+        fprintf(stderr, "[glu_hip] scratch placement skipped: %zu MiB free, the search wants %zu MiB; plain allocation\n", p.free_mib, p.want_mib);
+    if (glu_verbose() && p.found)
         fprintf(stderr, "[glu_hip] scratch placement: value array behind a %u MiB spacer, calibration sort %.3f ms (slowest candidate %.3f ms)\n",
-                best.spacer, best.ms, worst);
-    return cleanup(GLU_OK);
+                p.spacer_mib, p.ms, p.worst_ms);
+    return GLU_OK;
 }
 
 // A PAIR of arrays for the caller's side of a sort, placed by measurement against a sorter whose own scratch is in place:
@@ -715,106 +644,18 @@ glu_status tune_scratch_placement(glu_radix_sort_s* s, size_t count, size_t key_
 glu_status place_pair_by_measurement(glu_radix_sort_s* s, size_t count, Scratch& keys, Scratch& vals)
 {
     const size_t bytes = count * sizeof(uint32_t);
-    auto plain = [&]() -> glu_status {
-        GLU_TRY(keys.reserve(bytes));
-        return vals.reserve(bytes);
-    };
     if (keys.size >= bytes && vals.size >= bytes) return GLU_OK;
-    if (!s->tune_scratch || bytes < kTuneMinKeyBytes || s->keys.size < bytes || s->vals.size < bytes) return plain();
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return plain();
-    keys.release();
-    vals.release();
-    const size_t step_mib = 512, candidates = 16;
-    if (free_b < 2 * (2 * bytes + ((candidates - 1) * step_mib << 20)) + ((size_t) 1 << 30))
+    Placement p;
+    if (s->tune_scratch && bytes >= kTuneMinKeyBytes && s->keys.size >= bytes && s->vals.size >= bytes)
     {
-        if (glu_verbose()) fprintf(stderr, "[glu_hip] pair placement skipped: %zu MiB free; plain allocation\n", free_b >> 20);
-        return plain();
+        GLU_TRY(search_placement(s, PlacementSearch{"pair", "pair candidate", &keys, &vals, bytes, bytes, count, sizeof(uint32_t), nullptr}, p));
+        if (glu_verbose() && p.short_of_memory) fprintf(stderr, "[glu_hip] pair placement skipped: %zu MiB free; plain allocation\n", p.free_mib);
+        if (glu_verbose() && p.found)
+            fprintf(stderr, "[glu_hip] pair placement: %u candidates, calibration sort %.3f ms (slowest %.3f ms)\n", p.tried, p.ms, p.worst_ms);
     }
-    if (hipDeviceSynchronize() != hipSuccess) return fail(GLU_ERROR_DEVICE, "hipDeviceSynchronize failed before the pair placement");
-    hipStream_t st = g_dev.queue;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-    {
-        if (e0) (void) hipEventDestroy(e0);
-        return plain();
-    }
-    struct Cand { void* k = nullptr; void* v = nullptr; double ms = 1e30; } best;
-    double worst = 0;
-    uint32_t tried = 0;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const int was_profiling = s->profiling;
-    s->profiling = 0;
-    s->tuning = true; // (the sorts below must not start a search of their own)
-    glu_status status = GLU_OK;
-    for (size_t i = 0; i < candidates && status == GLU_OK; i++)
-    {
-        void *k = nullptr, *sp = nullptr, *v = nullptr;
-        if (hipMalloc(&k, bytes) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            break;
-        }
-        if (i && hipMalloc(&sp, i * step_mib << 20) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            (void) hipFree(k);
-            continue;
-        }
-        if (hipMalloc(&v, bytes) != hipSuccess)
-        {
-            (void) hipGetLastError();
-            (void) hipFree(k);
-            if (sp) (void) hipFree(sp);
-            continue;
-        }
-        if (sp) (void) hipFree(sp);
-        double ms = 1e30;
-        for (int rep = 0; rep < 3 && status == GLU_OK; rep++) // the first run is a warm-up
-        {
-            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) k, bytes / 4, 0x5EEDu + rep);
-            hipLaunchKernelGGL(tune_fill_kernel, dim3(g_dev.num_cus * 8), dim3(256), 0, st, (uint32_t*) v, bytes / 4, 77u);
-            (void) hipEventRecord(e0, st);
-            status = sort_run<uint32_t>(s, (uint32_t*) k, (uint32_t*) v, count, 0, st);
-            (void) hipEventRecord(e1, st);
-            if (status == GLU_OK && hipEventSynchronize(e1) == hipSuccess && rep > 0)
-            {
-                float t = 0;
-                if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms = std::min(ms, (double) t);
-            }
-        }
-        (void) hipStreamSynchronize(st);
-        if (glu_verbose()) fprintf(stderr, "[glu_hip]   pair candidate: keys %p values %p (spacer %zu MiB): %.3f ms\n", k, v, i * step_mib, ms);
-        if (ms < 1e29) worst = std::max(worst, ms);
-        if (status == GLU_OK && ms < best.ms)
-        {
-            if (best.k) (void) hipFree(best.k);
-            if (best.v) (void) hipFree(best.v);
-            best.k = k, best.v = v, best.ms = ms;
-        }
-        else
-        {
-            (void) hipFree(k);
-            (void) hipFree(v);
-        }
-        tried++;
-        if (tried >= 8 && best.ms <= 0.93 * worst) break;
-        if (std::chrono::steady_clock::now() - t_begin > std::chrono::milliseconds(1000)) break;
-    }
-    s->tuning = false;
-    s->profiling = was_profiling;
-    s->last_planned = false;
-    (void) hipEventDestroy(e0);
-    (void) hipEventDestroy(e1);
-    if (best.k)
-    {
-        keys.ptr = best.k, keys.size = bytes;
-        vals.ptr = best.v, vals.size = bytes;
-        if (glu_verbose())
-            fprintf(stderr, "[glu_hip] pair placement: %u candidates, calibration sort %.3f ms (slowest %.3f ms)\n", tried, best.ms, worst);
-    }
-    if (status != GLU_OK) return status;
-    return best.k ? GLU_OK : plain();
+    if (p.found) return GLU_OK;
+    GLU_TRY(keys.reserve(bytes));
+    return vals.reserve(bytes);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1159,7 +1000,7 @@ const SortOption kSortOptions[] = {
     GLU_OPT("SEG_MAX_GEO", s->seg_max_geo = (uint32_t) std::min<long long>(std::max<long long>(v, 1), 5)),
     GLU_OPT("SEG_SPLIT_GEO", s->seg_split_geo = (uint32_t) std::min<long long>(std::max<long long>(v, 1), 4)),
     GLU_OPT("SORT_FINISH_MIN", s->finish_min = (size_t) v),
-    GLU_OPT("SORT_FINISH_BACKOFF", s->finish_backoff = (uint32_t) std::max<long long>(0, v)),
+    GLU_OPT("SORT_FINISH_BACKOFF", s->feedback.finish_backoff = (uint32_t) std::max<long long>(0, v)),
     GLU_OPT("SORT_PAIR_UNIT_DIV", if (v >= 0) s->pair_unit_div = (uint32_t) v), // 0: no limit
     GLU_OPT("SORT_NT_STORES", s->nt_stores = v != 0),
     GLU_OPT("SORT_NT_MIN_BYTES", s->nt_min_bytes = (size_t) v),

@@ -13,6 +13,7 @@
 
 #include "glu_batch_host.hpp"
 #include "radix_sort_kernels.hpp"
+#include "sort_call_plan.hpp"
 
 namespace glu_hip
 {
@@ -152,7 +153,7 @@ struct glu_radix_sort_s
     bool no_fused_scan = false;   // GLU_HIP_SORT_NO_FUSED_SCAN=1: always launch the row-scan kernel (tests / tuning)
     bool no_plan = false;         // GLU_HIP_SORT_NO_PLAN=1: never skip constant-digit passes (tests / tuning)
     bool tune_scratch = true;     // GLU_HIP_SCRATCH_TUNE=0: take the first allocation of the scratch arrays (see tune_scratch_placement)
-    bool tuning = false;          // (inside tune_scratch_placement)
+    bool tuning = false;          // (inside search_placement)
     uint32_t tuned_spacer_mib = 0, tuned_candidates = 0; double tuned_ms = 0, tuned_worst_ms = 0; // what the last tuning saw and chose
     bool no_lines = false;        // GLU_HIP_SORT_NO_LINES=1: never use the 128-byte-line scatter kernel (tests / tuning)
     bool nt_stores = true;        // GLU_HIP_SORT_NT_STORES=0: plain instead of non-temporal line stores in the line scatter (tuning)
@@ -179,13 +180,22 @@ struct glu_radix_sort_s
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_unit = nullptr, ev_fork2 = nullptr, ev_join = nullptr;
     bool fork_behind = true;      // GLU_HIP_SORT_FORK=0: one queue, as in round 5 (tests / tuning)
+    bool side_forked = false;     // the side stream waits on ev_fork and has not joined the caller's queue yet (sort_bits joins it on every way out)
     bool ensure_side()
     {
-        if (side) return true;
-        if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) return side = nullptr, false;
+        if (side) return true; // (made last: it stands for the four events too)
+        bool ok = true;
         for (hipEvent_t* e : {&ev_fork, &ev_unit, &ev_fork2, &ev_join})
-            if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return false;
-        return true;
+            ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+        if (ok && hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess) return true;
+        // all or nothing: the next sort tries again, this one runs on one queue
+        for (hipEvent_t* e : {&ev_fork, &ev_unit, &ev_fork2, &ev_join})
+        {
+            if (*e) (void) hipEventDestroy(*e);
+            *e = nullptr;
+        }
+        side = nullptr;
+        return false;
     }
     bool lds_finish = true;       // GLU_HIP_SORT_LDS_FINISH=0: always the four passes of the ordinary sort (tests / tuning)
     bool long_runs = true;        // GLU_HIP_SORT_LONG_RUNS=0: a run longer than the in-LDS pass's tile refuses the whole sort, as in round 4 (tests / tuning)
@@ -197,18 +207,10 @@ struct glu_radix_sort_s
     // ran four passes: 4.5 instead of 3.0 ms).  GLU_HIP_SORT_FINISH_BACKOFF=N brings that back: a sort call that finds its LAST
     // attempt refused skips the next N attempts (no synchronisation: an outcome that is not there yet counts as unknown).
     uint32_t* finish_hint = nullptr;
-    uint32_t finish_seq = 0, finish_seq_acted_on = 0, finish_wait = 0;
-    uint32_t finish_last_geo = 0; // the tile geometry the device chose for the last sort whose outcome is known (0: none yet)
-    bool finish_last_refused = false; // the last attempt whose outcome is known was refused (see `side`)
-    // The runs of a sort that ends in LDS are the values of the 16 key bits below `top`: the whole key's top 16 by default,
-    // the top 16 of the bits that VARIED in this object's last attempt once that is known (keys below 2^28 make 4096 runs of the
-    // whole key's top bits and 65536 of bits [12, 28)).  A guess: the plan kernel refuses if a bit from `top` up varies after all.
-    bool device_top = true;       // GLU_HIP_SORT_DEVICE_TOP=0: the round-4 rule below (the host guesses from the object's last attempt)
-    uint32_t top_floor = 0;       // device_top: the exact top bit of an attempt whose sample missed a varying bit (handed to the next sample)
+    FinishFeedback feedback;      // what the attempts so far came to, and what the next one assumes (sort_call_plan.hpp: finish_attempts)
+    bool device_top = true;       // GLU_HIP_SORT_DEVICE_TOP=0: the round-4 rule (the host guesses the top bit from the object's last attempt)
     bool last_device_top = false; // (glu_radix_sort_read_finish reads the top bit from the device's plan)
-    uint32_t finish_top = 0;      // 0: the key's width
     uint32_t last_finish_top = 0; // what the last sort assumed (glu_radix_sort_read_finish)
-    uint32_t finish_backoff = 0;  // GLU_HIP_SORT_FINISH_BACKOFF=N (0, the default: every sort attempts)
     bool last_finish_attempted = false; // the last sort enqueued both sequences (glu_radix_sort_read_finish)
     bool last_finish_long_ok = false;   // ... and the segmented passes for runs longer than the tile (glu_radix_sort_read_long_runs)
     uint32_t last_finish_capacity = 0;  // and the longest run its last pass would take
@@ -236,7 +238,7 @@ struct glu_radix_sort_s
     // end in LDS, 2 = its in-LDS pass (glu_radix_sort_read_profile books them by which of the two sequences ran); 3 = the
     // counting pass of a SEGMENTED sort that tries to end in LDS, 4 = an ordinary segmented pass enqueued behind such an attempt
     std::vector<uint8_t> pass_kinds;
-    // (round 6) which attempt a pass belongs to (finish_seq; 0: none): glu_radix_sort_read_profile books every sort of a window by
+    // (round 6) which attempt a pass belongs to (FinishFeedback::finish_seq; 0: none): glu_radix_sort_read_profile books every sort of a window by
     // ITS outcome -- the plan kernel notes them in a ring of 256 (finish_outcomes) -- not by the last sort's
     std::vector<uint32_t> pass_seqs;
     uint32_t cur_seq = 0;

@@ -252,6 +252,7 @@ glu_status launch_pass_lines(glu_radix_sort_s* s, const KeyT* src_k, const uint3
         {
             HIP_TRY(hipEventRecord(s->ev_fork, stream));
             HIP_TRY(hipStreamWaitEvent(s->side, s->ev_fork, 0));
+            s->side_forked = true; // (sort_bits joins it, whichever way it returns)
         }
     }
     s->mark(stream, true);
