@@ -32,7 +32,7 @@ inline glu_status check_key_type(int key_type)
 }
 inline uint32_t key_bytes_of(int key_type) { return key_type >= (int) GLU_KEY_UINT64 ? 8u : 4u; }
 // how the kernels turn a key into its unsigned sort order: the values of KEY_XF_NONE, _SIGNED and _FLOAT of radix_sort_kernels.hpp
-// (glu_sort_batch.hip holds them equal)
+// (every unit that hands one to a kernel holds them equal by static_assert)
 constexpr uint32_t kKeyXfNone = 0, kKeyXfSigned = 1, kKeyXfFloat = 2;
 inline uint32_t key_xf_of(int key_type)
 {
@@ -128,6 +128,13 @@ inline glu_status check_items_aligned(const void* items, const void* out_items, 
 inline glu_status check_not_null(const void* ptr, const char* name)
 {
     return ptr ? GLU_OK : fail(GLU_ERROR_INVALID_ARGUMENT, "%s is NULL", name);
+}
+// several pointers under one sentence of the unit's own ("NULL argument", "NULL array", "Invalid key buffer"): the whole message
+inline glu_status check_none_null(std::initializer_list<const void*> ptrs, const char* message)
+{
+    for (const void* ptr : ptrs)
+        if (!ptr) return fail(GLU_ERROR_INVALID_ARGUMENT, "%s", message);
+    return GLU_OK;
 }
 template<typename T, typename V>
 inline void store(T* out, V value)

@@ -307,11 +307,11 @@ glu_status glu_dist_create(const void* unique_id, size_t id_bytes, int world_siz
 {
     GLU_TRY(enter());
     GLU_TRY(rccl_ready());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
+    GLU_TRY(check_not_null(out, "out"));
     if (!unique_id || id_bytes < sizeof(ncclUniqueId)) return fail(GLU_ERROR_INVALID_ARGUMENT, "unique_id must hold %zu bytes", sizeof(ncclUniqueId));
     if (world_size < 1 || rank < 0 || rank >= world_size) return fail(GLU_ERROR_INVALID_ARGUMENT, "bad rank %d of %d", rank, world_size);
     glu_dist_s* d = new (std::nothrow) glu_dist_s();
-    if (!d) return fail(GLU_ERROR_OUT_OF_MEMORY, "out of host memory");
+    if (d == nullptr) return fail(GLU_ERROR_OUT_OF_MEMORY, "out of host memory");
     d->world = world_size;
     d->rank = rank;
     d->owner.assign(kDistBuckets, 0);
@@ -360,7 +360,7 @@ glu_status glu_dist_create(const void* unique_id, size_t id_bytes, int world_siz
 
 glu_status glu_dist_destroy(glu_dist d)
 {
-    if (!d) return GLU_OK;
+    if (d == nullptr) return GLU_OK; // (NULL is fine, and asks for no device)
     GLU_TRY(enter());
     (void) hipDeviceSynchronize();
     if (d->comm) (void) rccl().CommDestroy(d->comm);
@@ -390,22 +390,22 @@ glu_status glu_dist_destroy(glu_dist d)
 
 glu_status glu_dist_partition_shift(glu_dist d, uint32_t* shift)
 {
-    if (!d || !shift) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
-    *shift = d->partition_shift;
+    GLU_TRY(check_none_null({d, shift}, "NULL argument"));
+    store(shift, d->partition_shift);
     return GLU_OK;
 }
 
 glu_status glu_dist_world(glu_dist d, int* world_size, int* rank)
 {
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
-    if (world_size) *world_size = d->world;
-    if (rank) *rank = d->rank;
+    GLU_TRY(check_not_null(d, "dist"));
+    store(world_size, d->world);
+    store(rank, d->rank);
     return GLU_OK;
 }
 
 glu_status glu_dist_local_sorter(glu_dist d, glu_radix_sort* out)
 {
-    if (!d || !out) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
+    GLU_TRY(check_none_null({d, out}, "NULL argument"));
     *out = d->sorter; // owned by `d`: for glu_radix_sort_set_digit_bits / set_profiling / read_profile, not for destroy
     return GLU_OK;
 }
@@ -413,7 +413,7 @@ glu_status glu_dist_local_sorter(glu_dist d, glu_radix_sort* out)
 glu_status glu_dist_prepare(glu_dist d, size_t local_count, size_t recv_capacity)
 {
     GLU_TRY(enter());
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     // the local sorter first: partition pass: table only; local sort: scratch for the receive side (the landing arrays of the
     // exchange), placed by measurement
     GLU_TRY(sort_prepare(d->sorter, std::max(local_count, recv_capacity), sizeof(uint32_t), true, /*may_place=*/true));
@@ -440,7 +440,7 @@ glu_status glu_dist_prepare(glu_dist d, size_t local_count, size_t recv_capacity
 glu_status glu_dist_set_reserved_cus(glu_dist d, int cus)
 {
     GLU_TRY(enter());
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     if (cus < 0 || cus * 4 >= g_dev.num_cus) return fail(GLU_ERROR_INVALID_ARGUMENT, "cannot reserve %d of %d CUs", cus, g_dev.num_cus);
     d->reserved_cus = cus;
     d->sorter->reserved_cus = (uint32_t) cus; // every pass: (CUs - reserved) x workgroups per CU of its geometry
@@ -449,7 +449,7 @@ glu_status glu_dist_set_reserved_cus(glu_dist d, int cus)
 
 glu_status glu_dist_set_profiling(glu_dist d, int enable)
 {
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     d->profiling = enable != 0;
     return GLU_OK;
 }
@@ -457,7 +457,7 @@ glu_status glu_dist_set_profiling(glu_dist d, int enable)
 glu_status glu_dist_phase_times(glu_dist d, double* ms4, uint64_t* sorts)
 {
     GLU_TRY(enter());
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     double sum[4] = {0, 0, 0, 0};
     uint64_t n = 0;
     for (size_t i = 0; i < d->marks_used; i++)
@@ -474,7 +474,7 @@ glu_status glu_dist_phase_times(glu_dist d, double* ms4, uint64_t* sorts)
     d->marks_used = 0;
     for (int i = 0; i < 4; i++)
         if (ms4) ms4[i] = n ? sum[i] / (double) n : 0.0;
-    if (sorts) *sorts = n;
+    store(sorts, n);
     return GLU_OK;
 }
 
@@ -515,7 +515,7 @@ glu_status glu_dist_sort_begin(glu_dist d, const uint32_t* keys, const uint32_t*
                                size_t* recv_count)
 {
     GLU_TRY(enter());
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     hipStream_t st = pick_stream(stream);
     d->began = false;
     // rank-local findings: remembered, not returned -- the rank still takes part in the histogram exchange
@@ -528,7 +528,7 @@ glu_status glu_dist_sort_begin(glu_dist d, const uint32_t* keys, const uint32_t*
             local_message = g_last_error;
         }
     };
-    if (local_count > 0 && (!keys || !vals)) note(fail(GLU_ERROR_INVALID_ARGUMENT, "NULL array"));
+    if (local_count > 0) note(check_none_null({keys, vals}, "NULL array"));
     if (local_count > kDistShardLimit) note(fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu does not fit 32-bit indexing", local_count));
     note(d->part_k.reserve(std::max<size_t>(local_count, 1) * sizeof(uint32_t)));
     note(d->part_v.reserve(std::max<size_t>(local_count, 1) * sizeof(uint32_t)));
@@ -642,7 +642,7 @@ glu_status glu_dist_sort_begin(glu_dist d, const uint32_t* keys, const uint32_t*
     d->local_count = local_count;
     d->recv_total = total;
     d->began = true;
-    if (recv_count) *recv_count = (size_t) total;
+    store(recv_count, total);
     return GLU_OK;
 }
 
@@ -687,7 +687,7 @@ glu_status dist_sort_finish(glu_dist_s* d, uint32_t* recv_keys, uint32_t* recv_v
         }
     };
     if (n_recv > capacity) note(fail(GLU_ERROR_INVALID_ARGUMENT, "receive arrays hold %zu pairs, %zu arrive", capacity, n_recv));
-    if (n_recv > 0 && (!recv_keys || !recv_vals)) note(fail(GLU_ERROR_INVALID_ARGUMENT, "NULL receive array"));
+    if (n_recv > 0) note(check_none_null({recv_keys, recv_vals}, "NULL receive array"));
     if (d->test_fail_finish == d->rank) note(fail(GLU_ERROR_OUT_OF_MEMORY, "injected failure of rank %d (GLU_HIP_DIST_TEST_FAIL)", d->rank));
     if (local == GLU_OK && n_recv > 1) note(sort_prepare(d->sorter, n_recv, sizeof(uint32_t), true));
 
@@ -922,7 +922,7 @@ extern "C" {
 glu_status glu_dist_sort_finish(glu_dist d, uint32_t* recv_keys, uint32_t* recv_vals, size_t capacity, void* stream)
 {
     GLU_TRY(enter());
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     return dist_sort_finish(d, recv_keys, recv_vals, capacity, pick_stream(stream), GLU_OK);
 }
 
@@ -954,15 +954,15 @@ glu_status glu_dist_sort_ptr(glu_dist d, const uint32_t* keys, const uint32_t* v
     }
     const size_t capacity = grown == GLU_OK ? std::min(d->recv_k.size, d->recv_v.size) / sizeof(uint32_t) : 0;
     GLU_TRY(dist_sort_finish(d, (uint32_t*) d->recv_k.ptr, (uint32_t*) d->recv_v.ptr, capacity, pick_stream(stream), grown));
-    if (out_keys) *out_keys = (uint32_t*) d->recv_k.ptr;
-    if (out_vals) *out_vals = (uint32_t*) d->recv_v.ptr;
-    if (out_count) *out_count = n_recv;
+    store(out_keys, (uint32_t*) d->recv_k.ptr);
+    store(out_vals, (uint32_t*) d->recv_v.ptr);
+    store(out_count, n_recv);
     return GLU_OK;
 }
 
 glu_status glu_dist_set_rounds(glu_dist d, int rounds)
 {
-    if (!d) return fail(GLU_ERROR_INVALID_ARGUMENT, "dist is NULL");
+    GLU_TRY(check_not_null(d, "dist"));
     if (rounds < 1 || rounds > glu_dist_s::kMaxRounds) return fail(GLU_ERROR_INVALID_ARGUMENT, "rounds must be 1 .. %d (got %d)", glu_dist_s::kMaxRounds, rounds);
     d->rounds = rounds; // (every rank must set the same value: the rounds are part of the message sequence)
     return GLU_OK;
@@ -970,15 +970,15 @@ glu_status glu_dist_set_rounds(glu_dist d, int rounds)
 
 glu_status glu_dist_last_rounds(glu_dist d, uint32_t* rounds)
 {
-    if (!d || !rounds) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
-    *rounds = d->last_rounds;
+    GLU_TRY(check_none_null({d, rounds}, "NULL argument"));
+    store(rounds, d->last_rounds);
     return GLU_OK;
 }
 
 glu_status glu_dist_last_local_sort(glu_dist d, uint32_t* segmented)
 {
-    if (!d || !segmented) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
-    *segmented = d->last_local_sort;
+    GLU_TRY(check_none_null({d, segmented}, "NULL argument"));
+    store(segmented, d->last_local_sort);
     return GLU_OK;
 }
 

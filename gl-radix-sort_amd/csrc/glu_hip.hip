@@ -94,14 +94,6 @@ glu_status sort_prepare(glu_radix_sort_s* s, size_t count, size_t key_size, bool
     return GLU_OK;
 }
 
-
-} // namespace
-glu_status glu_hip::host::sort_prepare_plain(glu_radix_sort_s* s, size_t count, size_t key_size, bool with_vals)
-{
-    return sort_prepare(s, count, key_size, with_vals, false);
-}
-namespace
-{
 // n <= one tile: the whole sort in a single workgroup / single launch (always 8-bit digits: the result does not
 // depend on the digit width)
 template<typename KeyT, int THREADS, int KPT, bool XF>
@@ -1007,6 +999,98 @@ const SortOption kSortOptions[] = {
     GLU_OPT("SORT_LARGE_MIN", s->large_min = (size_t) v),
 };
 #undef GLU_OPT
+
+static_assert(kKeyXfNone == KEY_XF_NONE && kKeyXfSigned == KEY_XF_SIGNED && kKeyXfFloat == KEY_XF_FLOAT, "key_xf_of() speaks the kernels' KEY_XF_*");
+
+// ---- what the entry points below share (which checks each makes, and in which order: the record of tests/test_gpu_refusals.py)
+
+// The sort of whole keys of a key type (checked by the caller): the sort of its key width with its order transform.
+glu_status sort_typed(glu_radix_sort_s* s, void* keys, uint32_t* vals, size_t count, int key_type, hipStream_t stream)
+{
+    const uint32_t xf = key_xf_of(key_type);
+    return key_bytes_of(key_type) == 8 ? sort_run<uint64_t>(s, (uint64_t*) keys, vals, count, 0, stream, xf)
+                                       : sort_run<uint32_t>(s, (uint32_t*) keys, vals, count, 0, stream, xf);
+}
+
+// glu_radix_sort_prepare, _prepare_u64 and _prepare_ex: the explicit prepare, which may place the scratch arrays by measurement
+glu_status prepare_entry(glu_radix_sort sort, size_t count, size_t key_bytes, bool with_vals)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(sort, "sort"));
+    if (key_bytes != 4 && key_bytes != 8) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bytes must be 4 or 8 (got %zu)", key_bytes);
+    return sort_prepare(sort, count, key_bytes, with_vals, true);
+}
+
+// The sorts of whole keys in the caller's arrays.  WITH_VALS: the entry point takes values, and requires them.
+template<typename KeyT, bool WITH_VALS>
+glu_status run_ptr_entry(glu_radix_sort sort, KeyT* keys, uint32_t* vals, size_t count, size_t num_steps, void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(sort, "sort"));
+    if (count == 0) return GLU_OK; // an empty shard: nothing to sort, NULL arrays are fine (torch gives data_ptr() == 0)
+    GLU_TRY(check_none_null({keys}, "Invalid key buffer"));
+    if (WITH_VALS) GLU_TRY(check_none_null({vals}, "Invalid value buffer"));
+    return sort_run<KeyT>(sort, keys, vals, count, num_steps, pick_stream(stream));
+}
+
+// The same in buffers of the registry, on the library's queue (RadixSort.hpp:275-276)
+template<typename KeyT, bool WITH_VALS>
+glu_status run_buffers_entry(glu_radix_sort sort, glu_buffer key_buffer, glu_buffer val_buffer, size_t count, size_t num_steps)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(sort, "sort"));
+    Buffer k, v;
+    GLU_TRY(lookup(key_buffer, k, "key buffer"));
+    if (WITH_VALS) GLU_TRY(lookup(val_buffer, v, "value buffer"));
+    if (count > 1 && (k.size / sizeof(KeyT) < count || (WITH_VALS && v.size / sizeof(uint32_t) < count)))
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu exceeds the %s buffer size", count, WITH_VALS ? "key/value" : "key");
+    return sort_run<KeyT>(sort, (KeyT*) k.ptr, (uint32_t*) v.ptr, count, num_steps, g_dev.queue);
+}
+
+// The piece arrays of a segmented call as SegPieces, and the elements they hold together.  Piece by piece: it names a segment below
+// num_segments and, where the call has a count (glu_radix_sort_run_segments_ptr; the plan has none: nullptr), lies inside [0, *count).
+glu_status read_pieces(const uint64_t* piece_begin, const uint64_t* piece_len, const uint32_t* piece_segment, size_t num_pieces,
+                       uint32_t num_segments, const size_t* count, std::vector<SegPiece>& pieces, uint64_t& total)
+{
+    pieces.resize(num_pieces);
+    total = 0;
+    for (size_t i = 0; i < num_pieces; i++)
+    {
+        if (piece_segment[i] >= num_segments) return fail(GLU_ERROR_INVALID_ARGUMENT, "piece %zu names segment %u of %u", i, piece_segment[i], num_segments);
+        if (count && (piece_begin[i] > *count || piece_len[i] > *count - piece_begin[i]))
+            return fail(GLU_ERROR_INVALID_ARGUMENT, "piece %zu [%llu, +%llu) exceeds count %zu", i, (unsigned long long) piece_begin[i],
+                        (unsigned long long) piece_len[i], *count);
+        pieces[i] = SegPiece{piece_begin[i], piece_len[i], piece_segment[i]};
+        total += piece_len[i];
+    }
+    return GLU_OK;
+}
+
+// Did the last sort on the object try to end in LDS?  (No plan yet: nothing was tried.)
+bool last_sort_tried(const glu_radix_sort_s* s) { return s->plan.ptr && s->last_planned && s->last_finish_attempted; }
+
+// The device's PassPlan of the last sort where it `ran_with` one, else zeros
+glu_status read_device_plan(const glu_radix_sort_s* s, bool ran_with, PassPlan& host)
+{
+    memset(&host, 0, sizeof(host));
+    if (ran_with) HIP_TRY(hipMemcpy(&host, s->plan.ptr, sizeof(host), hipMemcpyDeviceToHost));
+    return GLU_OK;
+}
+
+// Did the last segmented sort try to end in LDS, and if so the longest run its first pass found (a device word)
+glu_status read_seg_gate(const glu_radix_sort_s* s, bool& tried, uint32_t& longest)
+{
+    tried = s->last_seg_finish_attempted && s->seg_gate.ptr;
+    longest = 0;
+    if (tried) HIP_TRY(hipMemcpy(&longest, s->seg_gate.ptr, sizeof(longest), hipMemcpyDeviceToHost));
+    return GLU_OK;
+}
+} // namespace
+
+// The lazy allocation at the head of a sort, for the batched sort's translation unit
+glu_status glu_hip::host::sort_prepare_plain(glu_radix_sort_s* s, size_t count, size_t key_size, bool with_vals)
+{
+    return sort_prepare(s, count, key_size, with_vals, false);
 }
 
 // The ordinary typed sort as a linear chain on `stream`.  The sort's only fork is the side stream of a sort that tries to end in LDS
@@ -1017,11 +1101,7 @@ glu_status glu_hip::host::sort_typed_one_queue(glu_radix_sort_s* s, void* keys, 
 {
     const bool fork = s->fork_behind;
     s->fork_behind = false;
-    const uint32_t xf = (key_type == GLU_KEY_INT32 || key_type == GLU_KEY_INT64)       ? KEY_XF_SIGNED
-                        : (key_type == GLU_KEY_FLOAT32 || key_type == GLU_KEY_FLOAT64) ? KEY_XF_FLOAT
-                                                                                       : KEY_XF_NONE;
-    const glu_status status = (int) key_type >= (int) GLU_KEY_UINT64 ? sort_run<uint64_t>(s, (uint64_t*) keys, vals, count, 0, stream, xf)
-                                                                     : sort_run<uint32_t>(s, (uint32_t*) keys, vals, count, 0, stream, xf);
+    const glu_status status = sort_typed(s, keys, vals, count, key_type, stream);
     s->fork_behind = fork;
     return status;
 }
@@ -1030,179 +1110,87 @@ extern "C" {
 
 glu_status glu_radix_sort_create(glu_radix_sort* out)
 {
-    GLU_TRY(enter());
-    if (!out) return fail(GLU_ERROR_INVALID_ARGUMENT, "out is NULL");
-    glu_radix_sort_s* s = new glu_radix_sort_s();
     // the process environment as DEFAULTS for new objects (GLU_HIP_<OPTION>=value, read here, when an object is created);
     // programs and tests set options on the object: glu_radix_sort_set_option
-    for (const SortOption& o : kSortOptions)
-    {
-        char name[96];
-        snprintf(name, sizeof(name), "GLU_HIP_%s", o.name);
-        if (const char* e = glu_env(name)) o.set(s, atoll(e));
-    }
-    *out = s;
-    return GLU_OK;
+    return create_object(out, [](glu_radix_sort_s& s) {
+        for (const SortOption& o : kSortOptions)
+        {
+            char name[96];
+            snprintf(name, sizeof(name), "GLU_HIP_%s", o.name);
+            if (const char* e = glu_env(name)) o.set(&s, atoll(e));
+        }
+        return GLU_OK;
+    });
 }
 
-glu_status glu_radix_sort_destroy(glu_radix_sort sort)
+// the object may last have been used on a caller's stream (the *_ptr entry points): destroy_object drains the device, not only the
+// library queue, before everything the object owns goes away (RAII of the reference: RadixSort.hpp:194-200, gl_utils.hpp:184-188)
+glu_status glu_radix_sort_destroy(glu_radix_sort sort) { return destroy_object(sort); }
+
+glu_status glu_radix_sort_prepare(glu_radix_sort sort, size_t count) { return prepare_entry(sort, count, sizeof(uint32_t), true); }
+
+glu_status glu_radix_sort_prepare_ex(glu_radix_sort sort, size_t count, size_t key_bytes, int with_vals) { return prepare_entry(sort, count, key_bytes, with_vals != 0); }
+
+glu_status glu_radix_sort_prepare_u64(glu_radix_sort sort, size_t count) { return prepare_entry(sort, count, sizeof(uint64_t), true); }
+
+glu_status glu_radix_sort_run_ptr(glu_radix_sort sort, uint32_t* keys, uint32_t* vals, size_t count, size_t num_steps, void* stream)
 {
-    GLU_TRY(enter());
-    if (!sort) return GLU_OK;
-    // the object may last have been used on a caller's stream (the *_ptr entry points): drain the device, not only the
-    // library queue, before its scratch goes away (RAII of the reference: RadixSort.hpp:194-200, gl_utils.hpp:184-188)
-    (void) hipDeviceSynchronize();
-    for (Scratch* sc : {&sort->keys, &sort->vals, &sort->table, &sort->plan, &sort->pair_t2, &sort->pair_table, &sort->pair_ranges,
-                        &sort->pair_sub, &sort->pair_wide, &sort->seg_desc, &sort->seg_zero, &sort->finish_lengths, &sort->finish_starts, &sort->finish_crowded, &sort->finish_outcomes, &sort->seg_gate, &sort->long_image, &sort->long_hdr, &sort->long_bits, &sort->batch_lists})
-        sc->release();
-    if (sort->finish_hint) (void) hipHostFree(sort->finish_hint);
-    for (hipEvent_t e : {sort->ev_fork, sort->ev_unit, sort->ev_fork2, sort->ev_join})
-        if (e) (void) hipEventDestroy(e);
-    if (sort->side) (void) hipStreamDestroy(sort->side);
-    for (hipEvent_t e : sort->events) (void) hipEventDestroy(e);
-    for (glu_radix_sort_s::SegStage& st : sort->seg_stage)
-    {
-        if (st.host) (void) hipHostFree(st.host);
-        if (st.copied) (void) hipEventDestroy(st.copied);
-    }
-    delete sort;
-    return GLU_OK;
+    return run_ptr_entry<uint32_t, true>(sort, keys, vals, count, num_steps, stream);
 }
 
-glu_status glu_radix_sort_prepare(glu_radix_sort sort, size_t count)
+glu_status glu_radix_sort_run_u64_ptr(glu_radix_sort sort, uint64_t* keys, uint32_t* vals, size_t count, size_t num_steps, void* stream)
 {
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    return sort_prepare(sort, count, sizeof(uint32_t), true, true);
-}
-
-glu_status glu_radix_sort_prepare_ex(glu_radix_sort sort, size_t count, size_t key_bytes, int with_vals)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (key_bytes != 4 && key_bytes != 8) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bytes must be 4 or 8 (got %zu)", key_bytes);
-    return sort_prepare(sort, count, key_bytes, with_vals != 0, true);
-}
-
-glu_status glu_radix_sort_prepare_u64(glu_radix_sort sort, size_t count)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    return sort_prepare(sort, count, sizeof(uint64_t), true, true);
-}
-
-glu_status glu_radix_sort_run_ptr(glu_radix_sort sort, uint32_t* keys, uint32_t* vals, size_t count, size_t num_steps,
-                                  void* stream)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (count == 0) return GLU_OK; // an empty shard: nothing to sort, NULL arrays are fine (torch gives data_ptr() == 0)
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    if (!vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid value buffer");
-    return sort_run<uint32_t>(sort, keys, vals, count, num_steps, pick_stream(stream));
-}
-
-glu_status glu_radix_sort_run_u64_ptr(glu_radix_sort sort, uint64_t* keys, uint32_t* vals, size_t count,
-                                      size_t num_steps, void* stream)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (count == 0) return GLU_OK;
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    if (!vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid value buffer");
-    return sort_run<uint64_t>(sort, keys, vals, count, num_steps, pick_stream(stream));
-}
-
-glu_status glu_radix_sort_run(glu_radix_sort sort, glu_buffer key_buffer, glu_buffer val_buffer, size_t count,
-                              size_t num_steps)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    Buffer k, v;
-    GLU_TRY(lookup(key_buffer, k, "key buffer"));   // RadixSort.hpp:275
-    GLU_TRY(lookup(val_buffer, v, "value buffer")); // RadixSort.hpp:276
-    if (count > 1 && (k.size / sizeof(uint32_t) < count || v.size / sizeof(uint32_t) < count))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu exceeds the key/value buffer size", count);
-    return sort_run<uint32_t>(sort, (uint32_t*) k.ptr, (uint32_t*) v.ptr, count, num_steps, g_dev.queue);
-}
-
-glu_status glu_radix_sort_run_u64(glu_radix_sort sort, glu_buffer key_buffer, glu_buffer val_buffer, size_t count,
-                                  size_t num_steps)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    Buffer k, v;
-    GLU_TRY(lookup(key_buffer, k, "key buffer"));
-    GLU_TRY(lookup(val_buffer, v, "value buffer"));
-    if (count > 1 && (k.size / sizeof(uint64_t) < count || v.size / sizeof(uint32_t) < count))
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu exceeds the key/value buffer size", count);
-    return sort_run<uint64_t>(sort, (uint64_t*) k.ptr, (uint32_t*) v.ptr, count, num_steps, g_dev.queue);
+    return run_ptr_entry<uint64_t, true>(sort, keys, vals, count, num_steps, stream);
 }
 
 glu_status glu_radix_sort_run_keys_ptr(glu_radix_sort sort, uint32_t* keys, size_t count, size_t num_steps, void* stream)
 {
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (count == 0) return GLU_OK; // an empty shard: NULL arrays are fine
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    return sort_run<uint32_t>(sort, keys, nullptr, count, num_steps, pick_stream(stream));
+    return run_ptr_entry<uint32_t, false>(sort, keys, nullptr, count, num_steps, stream);
 }
 
 glu_status glu_radix_sort_run_keys_u64_ptr(glu_radix_sort sort, uint64_t* keys, size_t count, size_t num_steps, void* stream)
 {
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (count == 0) return GLU_OK;
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    return sort_run<uint64_t>(sort, keys, nullptr, count, num_steps, pick_stream(stream));
+    return run_ptr_entry<uint64_t, false>(sort, keys, nullptr, count, num_steps, stream);
 }
 
-glu_status glu_radix_sort_run_typed_ptr(glu_radix_sort sort, void* keys, uint32_t* vals, size_t count, glu_key_type key_type,
-                                        void* stream)
+glu_status glu_radix_sort_run(glu_radix_sort sort, glu_buffer key_buffer, glu_buffer val_buffer, size_t count, size_t num_steps)
+{
+    return run_buffers_entry<uint32_t, true>(sort, key_buffer, val_buffer, count, num_steps);
+}
+
+glu_status glu_radix_sort_run_u64(glu_radix_sort sort, glu_buffer key_buffer, glu_buffer val_buffer, size_t count, size_t num_steps)
+{
+    return run_buffers_entry<uint64_t, true>(sort, key_buffer, val_buffer, count, num_steps);
+}
+
+glu_status glu_radix_sort_run_keys(glu_radix_sort sort, glu_buffer key_buffer, size_t count, size_t num_steps)
+{
+    return run_buffers_entry<uint32_t, false>(sort, key_buffer, 0, count, num_steps);
+}
+
+glu_status glu_radix_sort_run_typed_ptr(glu_radix_sort sort, void* keys, uint32_t* vals, size_t count, glu_key_type key_type, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if ((int) key_type < (int) GLU_KEY_UINT32 || (int) key_type > (int) GLU_KEY_FLOAT64)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", (int) key_type);
+    GLU_TRY(check_not_null(sort, "sort"));
+    GLU_TRY(check_key_type(key_type));
     if (count == 0) return GLU_OK;
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
-    hipStream_t st = pick_stream(stream);
-    switch (key_type)
-    {
-    case GLU_KEY_UINT32: return sort_run<uint32_t>(sort, (uint32_t*) keys, vals, count, 0, st, KEY_XF_NONE);
-    case GLU_KEY_INT32: return sort_run<uint32_t>(sort, (uint32_t*) keys, vals, count, 0, st, KEY_XF_SIGNED);
-    case GLU_KEY_FLOAT32: return sort_run<uint32_t>(sort, (uint32_t*) keys, vals, count, 0, st, KEY_XF_FLOAT);
-    case GLU_KEY_UINT64: return sort_run<uint64_t>(sort, (uint64_t*) keys, vals, count, 0, st, KEY_XF_NONE);
-    case GLU_KEY_INT64: return sort_run<uint64_t>(sort, (uint64_t*) keys, vals, count, 0, st, KEY_XF_SIGNED);
-    case GLU_KEY_FLOAT64: return sort_run<uint64_t>(sort, (uint64_t*) keys, vals, count, 0, st, KEY_XF_FLOAT);
-    default: return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key type: %d", (int) key_type);
-    }
+    GLU_TRY(check_none_null({keys}, "Invalid key buffer"));
+    return sort_typed(sort, keys, vals, count, key_type, pick_stream(stream));
 }
 
 glu_status glu_radix_sort_run_bit_range_ptr(glu_radix_sort sort, void* keys, uint32_t* vals, size_t count, uint32_t key_bits,
                                             uint32_t begin_bit, uint32_t end_bit, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (key_bits != 32 && key_bits != 64) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bits must be 32 or 64 (got %u)", key_bits);
     if (begin_bit > end_bit || end_bit > key_bits)
         return fail(GLU_ERROR_INVALID_ARGUMENT, "bad bit range [%u, %u) for %u-bit keys", begin_bit, end_bit, key_bits);
     if (count == 0) return GLU_OK;
-    if (!keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid key buffer");
+    GLU_TRY(check_none_null({keys}, "Invalid key buffer"));
     hipStream_t st = pick_stream(stream);
     if (key_bits == 32) return sort_bits<uint32_t>(sort, (uint32_t*) keys, vals, count, begin_bit, end_bit, st);
     return sort_bits<uint64_t>(sort, (uint64_t*) keys, vals, count, begin_bit, end_bit, st);
-}
-
-glu_status glu_radix_sort_run_keys(glu_radix_sort sort, glu_buffer key_buffer, size_t count, size_t num_steps)
-{
-    GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    Buffer k;
-    GLU_TRY(lookup(key_buffer, k, "key buffer"));
-    if (count > 1 && k.size / sizeof(uint32_t) < count)
-        return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu exceeds the key buffer size", count);
-    return sort_run<uint32_t>(sort, (uint32_t*) k.ptr, nullptr, count, num_steps, g_dev.queue);
 }
 
 glu_status glu_radix_sort_partition_ptr(glu_radix_sort sort, const uint32_t* src_keys, const uint32_t* src_vals,
@@ -1210,10 +1198,10 @@ glu_status glu_radix_sort_partition_ptr(glu_radix_sort sort, const uint32_t* src
                                         uint32_t bits, uint32_t* digit_histogram, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (count > 0)
     {
-        if (!src_keys || !src_vals || !dst_keys || !dst_vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL array");
+        GLU_TRY(check_none_null({src_keys, src_vals, dst_keys, dst_vals}, "NULL array"));
         if (src_keys == dst_keys || src_vals == dst_vals)
             return fail(GLU_ERROR_INVALID_ARGUMENT, "partition needs distinct source and destination");
     }
@@ -1237,23 +1225,15 @@ glu_status glu_radix_sort_run_segments_ptr(glu_radix_sort sort, uint32_t* in_key
                                            uint32_t num_segments, uint32_t key_bits, void* stream)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (key_bits > 32 || key_bits % 8 != 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "key_bits must be 0, 8, 16, 24 or 32 (got %u)", key_bits);
     if (count > 0xFFFF0000ull) return fail(GLU_ERROR_INVALID_ARGUMENT, "count %zu does not fit 32-bit indexing", count);
-    if (num_pieces > 0 && (!piece_begin || !piece_len || !piece_segment)) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL piece array");
+    if (num_pieces > 0) GLU_TRY(check_none_null({piece_begin, piece_len, piece_segment}, "NULL piece array"));
     if (num_segments == 0 && num_pieces > 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "pieces but no segments");
     if (num_segments > kSegMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %u exceeds %u", num_segments, kSegMaxSegments);
-    std::vector<SegPiece> pieces(num_pieces);
+    std::vector<SegPiece> pieces;
     uint64_t total = 0;
-    for (size_t i = 0; i < num_pieces; i++)
-    {
-        if (piece_segment[i] >= num_segments) return fail(GLU_ERROR_INVALID_ARGUMENT, "piece %zu names segment %u of %u", i, piece_segment[i], num_segments);
-        if (piece_begin[i] > count || piece_len[i] > count - piece_begin[i])
-            return fail(GLU_ERROR_INVALID_ARGUMENT, "piece %zu [%llu, +%llu) exceeds count %zu", i, (unsigned long long) piece_begin[i],
-                        (unsigned long long) piece_len[i], count);
-        pieces[i] = SegPiece{piece_begin[i], piece_len[i], piece_segment[i]};
-        total += piece_len[i];
-    }
+    GLU_TRY(read_pieces(piece_begin, piece_len, piece_segment, num_pieces, num_segments, &count, pieces, total));
     if (total != count) return fail(GLU_ERROR_INVALID_ARGUMENT, "the pieces hold %llu elements, count is %zu", (unsigned long long) total, count);
     if (count == 0) return GLU_OK;
     {
@@ -1272,7 +1252,7 @@ glu_status glu_radix_sort_run_segments_ptr(glu_radix_sort sort, uint32_t* in_key
             end = sp.first + sp.second;
         }
     }
-    if (!in_keys || !in_vals || !out_keys || !out_vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL array");
+    GLU_TRY(check_none_null({in_keys, in_vals, out_keys, out_vals}, "NULL array"));
     if (in_keys == out_keys || in_vals == out_vals) return fail(GLU_ERROR_INVALID_ARGUMENT, "the segmented sort needs distinct input and output arrays");
     // the sub-block descriptors of a call travel through a ring of pinned staging buffers that later calls overwrite, and a
     // prepared sorter may wait for a staging buffer's previous copy: a captured graph would replay neither correctly
@@ -1292,18 +1272,13 @@ glu_status glu_radix_sort_plan_segments(const uint64_t* piece_begin, const uint6
                                         uint64_t* segment_start, size_t* num_sub_blocks)
 {
     // host only (no device needed): the cut of a segmented pass into sub-blocks, for inspection and tests
-    if (num_pieces > 0 && (!piece_begin || !piece_len || !piece_segment)) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL piece array");
+    if (num_pieces > 0) GLU_TRY(check_none_null({piece_begin, piece_len, piece_segment}, "NULL piece array"));
     if (num_workgroups == 0 || !num_sub_blocks) return fail(GLU_ERROR_INVALID_ARGUMENT, "bad arguments");
     if (num_segments > kSegMaxSegments) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_segments %u exceeds %u", num_segments, kSegMaxSegments);
     if (num_workgroups > (1u << 20)) return fail(GLU_ERROR_INVALID_ARGUMENT, "num_workgroups %u exceeds %u", num_workgroups, 1u << 20);
-    std::vector<SegPiece> pieces(num_pieces);
+    std::vector<SegPiece> pieces;
     uint64_t total = 0;
-    for (size_t i = 0; i < num_pieces; i++)
-    {
-        if (piece_segment[i] >= num_segments) return fail(GLU_ERROR_INVALID_ARGUMENT, "piece %zu names segment %u of %u", i, piece_segment[i], num_segments);
-        pieces[i] = SegPiece{piece_begin[i], piece_len[i], piece_segment[i]};
-        total += piece_len[i];
-    }
+    GLU_TRY(read_pieces(piece_begin, piece_len, piece_segment, num_pieces, num_segments, nullptr, pieces, total));
     if (total > 0xFFFF0000ull) return fail(GLU_ERROR_INVALID_ARGUMENT, "the pieces hold %llu elements: more than 32-bit indexing", (unsigned long long) total);
     std::stable_sort(pieces.begin(), pieces.end(), [](const SegPiece& a, const SegPiece& b) { return a.seg < b.seg; });
     std::vector<uint64_t> start((size_t) num_segments + 1, 0);
@@ -1324,7 +1299,7 @@ glu_status glu_radix_sort_plan_segments(const uint64_t* piece_begin, const uint6
 glu_status glu_radix_sort_set_digit_bits(glu_radix_sort sort, uint32_t bits)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (bits != 4 && bits != 8) return fail(GLU_ERROR_INVALID_ARGUMENT, "digit bits must be 4 or 8 (got %u)", bits);
     sort->digit_bits = bits;
     return GLU_OK;
@@ -1333,7 +1308,7 @@ glu_status glu_radix_sort_set_digit_bits(glu_radix_sort sort, uint32_t bits)
 glu_status glu_radix_sort_set_option(glu_radix_sort sort, const char* name, long long value)
 {
     GLU_TRY(enter());
-    if (!sort || !name) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort / name is NULL");
+    GLU_TRY(check_none_null({sort, name}, "sort / name is NULL"));
     if (strncasecmp(name, "GLU_HIP_", 8) == 0) name += 8; // (the environment's spelling is accepted)
     for (const SortOption& o : kSortOptions)
         if (strcasecmp(name, o.name) == 0)
@@ -1347,15 +1322,15 @@ glu_status glu_radix_sort_set_option(glu_radix_sort sort, const char* name, long
 glu_status glu_radix_sort_get_digit_bits(glu_radix_sort sort, uint32_t* bits)
 {
     GLU_TRY(enter());
-    if (!sort || !bits) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
-    *bits = sort->digit_bits;
+    GLU_TRY(check_none_null({sort, bits}, "NULL argument"));
+    store(bits, sort->digit_bits);
     return GLU_OK;
 }
 
 glu_status glu_radix_sort_set_profiling(glu_radix_sort sort, int enable)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     sort->profiling = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
     if (!enable) sort->events_used = 0, sort->slots.clear(), sort->pass_kinds.clear(), sort->pass_seqs.clear();
     return GLU_OK;
@@ -1364,16 +1339,15 @@ glu_status glu_radix_sort_set_profiling(glu_radix_sort sort, int enable)
 glu_status glu_radix_sort_read_plan(glu_radix_sort sort, uint32_t* skipped, uint32_t* counted_alone, uint32_t* pair_role, size_t passes)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     if (passes > (size_t) kPlanMaxPasses) return fail(GLU_ERROR_INVALID_ARGUMENT, "at most %d passes", kPlanMaxPasses);
     if (!sort->plan.ptr) return fail(GLU_ERROR_INVALID_STATE, "no sort has run on this object");
-    PassPlan host;
-    memset(&host, 0, sizeof(host));
     // a sort below 2^22 elements runs without a device-side plan: every pass ran, none was paired
-    if (sort->last_planned) HIP_TRY(hipMemcpy(&host, sort->plan.ptr, sizeof(host), hipMemcpyDeviceToHost));
+    PassPlan host;
+    GLU_TRY(read_device_plan(sort, sort->last_planned, host));
     // a sort that tried to end in LDS has its two top-bit passes in front of the ordinary ones, which are what this call
     // reports (glu_radix_sort_read_finish tells which of the two sequences ran)
-    const size_t first = sort->last_planned && sort->last_finish_attempted ? 2 : 0;
+    const size_t first = last_sort_tried(sort) ? 2 : 0;
     for (size_t p = 0; p < passes; p++)
     {
         const bool have = first + p < (size_t) kPlanMaxPasses;
@@ -1394,8 +1368,8 @@ glu_status glu_radix_sort_plan_finish(size_t count, uint32_t key_bytes, uint32_t
         first = finish_geometry_for(count);
         last = first ? std::min<uint32_t>(first + 2, kFinishGeometries) : 0u;
     }
-    if (first_capacity) *first_capacity = finish_geometry_capacity(first);
-    if (last_capacity) *last_capacity = finish_geometry_capacity(last);
+    store(first_capacity, finish_geometry_capacity(first));
+    store(last_capacity, finish_geometry_capacity(last));
     return GLU_OK;
 }
 
@@ -1403,30 +1377,30 @@ glu_status glu_radix_sort_read_seg_finish(glu_radix_sort sort, uint32_t* attempt
                                           uint32_t* capacity, uint32_t* runs, uint32_t* tile, uint32_t* split)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    const bool tried = sort->last_seg_finish_attempted && sort->seg_gate.ptr;
-    uint32_t longest = 0;
-    if (tried) HIP_TRY(hipMemcpy(&longest, sort->seg_gate.ptr, sizeof(longest), hipMemcpyDeviceToHost));
-    if (attempted) *attempted = tried ? 1u : 0u;
-    if (accepted) *accepted = tried && longest <= sort->last_seg_finish_capacity ? 1u : 0u;
-    if (longest_run) *longest_run = longest;
-    if (capacity) *capacity = tried ? sort->last_seg_finish_capacity : 0u;
-    if (runs) *runs = tried ? sort->last_seg_finish_runs : 0u;
-    if (tile) *tile = tried ? sort->last_seg_finish_tile : 0u;
-    if (split) *split = tried ? sort->last_seg_finish_split : 0u;
+    GLU_TRY(check_not_null(sort, "sort"));
+    bool tried;
+    uint32_t longest;
+    GLU_TRY(read_seg_gate(sort, tried, longest));
+    store(attempted, tried ? 1u : 0u);
+    store(accepted, tried && longest <= sort->last_seg_finish_capacity ? 1u : 0u);
+    store(longest_run, longest);
+    store(capacity, tried ? sort->last_seg_finish_capacity : 0u);
+    store(runs, tried ? sort->last_seg_finish_runs : 0u);
+    store(tile, tried ? sort->last_seg_finish_tile : 0u);
+    store(split, tried ? sort->last_seg_finish_split : 0u);
     return GLU_OK;
 }
 
 glu_status glu_radix_sort_read_long_runs(glu_radix_sort sort, uint32_t* runs, uint32_t* sub_blocks, uint32_t* pairs)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     uint32_t hdr[3] = {0, 0, 0};
-    const bool tried = sort->plan.ptr && sort->last_planned && sort->last_finish_attempted && sort->last_finish_long_ok && sort->long_hdr.ptr;
-    if (tried) HIP_TRY(hipMemcpy(hdr, sort->long_hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost));
-    if (runs) *runs = hdr[0];
-    if (sub_blocks) *sub_blocks = hdr[1];
-    if (pairs) *pairs = hdr[2];
+    if (last_sort_tried(sort) && sort->last_finish_long_ok && sort->long_hdr.ptr)
+        HIP_TRY(hipMemcpy(hdr, sort->long_hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost));
+    store(runs, hdr[0]);
+    store(sub_blocks, hdr[1]);
+    store(pairs, hdr[2]);
     return GLU_OK;
 }
 
@@ -1434,55 +1408,44 @@ glu_status glu_radix_sort_read_finish(glu_radix_sort sort, uint32_t* attempted, 
                                       uint32_t* capacity, uint32_t* top_bit)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    const bool tried = sort->plan.ptr && sort->last_planned && sort->last_finish_attempted; // (no plan yet: nothing was tried)
+    GLU_TRY(check_not_null(sort, "sort"));
+    const bool tried = last_sort_tried(sort);
     PassPlan host;
-    memset(&host, 0, sizeof(host));
-    if (tried) HIP_TRY(hipMemcpy(&host, sort->plan.ptr, sizeof(host), hipMemcpyDeviceToHost));
-    if (attempted) *attempted = tried ? 1u : 0u;
-    if (accepted) *accepted = tried && host.finish ? 1u : 0u;
-    if (longest_run) *longest_run = tried ? host.finish_longest : 0u;
+    GLU_TRY(read_device_plan(sort, tried, host));
+    store(attempted, tried ? 1u : 0u);
+    store(accepted, tried && host.finish ? 1u : 0u);
+    store(longest_run, tried ? host.finish_longest : 0u);
     if (tried && sort->last_device_top && host.top_bit) sort->last_finish_top = host.top_bit; // (chosen on the device)
     // the tile the device chose; refused: the largest one that was enqueued
-    if (capacity) *capacity = !tried ? 0u : host.finish ? finish_geometry_capacity(host.finish) : sort->last_finish_capacity;
-    if (top_bit) *top_bit = tried ? sort->last_finish_top : 0u;
+    store(capacity, !tried ? 0u : host.finish ? finish_geometry_capacity(host.finish) : sort->last_finish_capacity);
+    store(top_bit, tried ? sort->last_finish_top : 0u);
     return GLU_OK;
 }
 
-namespace
-{
 // Sums the recorded intervals.  Sorts that tried to end in LDS (radix_lds_finish.hpp) enqueue two sequences of passes, one of
 // which returns at once; which one is read from the plan of the LAST sort and assumed for every sort since the previous
 // read.  Booked are the passes that did the work: accepted -- the two top-bit passes (count / scan / scatter) and the in-LDS
 // pass (finish_ms); refused -- the ordinary passes, plus the count interval of the first top-bit pass (the price of asking).
-glu_status read_profile_impl(glu_radix_sort sort, double* count_ms, double* scan_ms, double* scatter_ms, uint64_t* passes,
-                             double* finish_ms, uint64_t* finish_passes)
+glu_status glu_radix_sort_read_profile_finish(glu_radix_sort sort, double* count_ms, double* scan_ms, double* scatter_ms,
+                                              uint64_t* passes, double* finish_ms, uint64_t* finish_passes)
 {
     GLU_TRY(enter());
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
+    GLU_TRY(check_not_null(sort, "sort"));
     double acc[3] = {0, 0, 0}, fin = 0;
     uint64_t live = 0, fin_n = 0;
     const size_t n = sort->slots.size() / 4;
     if (sort->events_used > 0) HIP_TRY(hipEventSynchronize(sort->events[sort->events_used - 1]));
-    bool accepted = false;
-    if (sort->last_planned && sort->last_finish_attempted && sort->plan.ptr)
-    {
-        PassPlan host;
-        HIP_TRY(hipMemcpy(&host, sort->plan.ptr, sizeof(host), hipMemcpyDeviceToHost));
-        accepted = host.finish != 0;
-    }
+    PassPlan host;
+    GLU_TRY(read_device_plan(sort, last_sort_tried(sort), host));
+    const bool last_accepted = host.finish != 0;
     // the outcome of every attempt of the window, by attempt number (a window of more than 256 sorts: the older ones by the last)
     std::vector<uint32_t> ring(256, 0u);
     const bool have_ring = sort->finish_outcomes.ptr != nullptr;
     if (have_ring) HIP_TRY(hipMemcpy(ring.data(), sort->finish_outcomes.ptr, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const bool last_accepted = accepted;
-    bool seg_accepted = false;
-    if (sort->last_seg_finish_attempted && sort->seg_gate.ptr)
-    {
-        uint32_t longest = 0;
-        HIP_TRY(hipMemcpy(&longest, sort->seg_gate.ptr, sizeof(longest), hipMemcpyDeviceToHost));
-        seg_accepted = longest <= sort->last_seg_finish_capacity;
-    }
+    bool seg_tried = false;
+    uint32_t seg_longest = 0;
+    GLU_TRY(read_seg_gate(sort, seg_tried, seg_longest));
+    const bool seg_accepted = seg_tried && seg_longest <= sort->last_seg_finish_capacity;
     for (size_t p = 0; p < n; p++)
     {
         float ms[3] = {0.f, 0.f, 0.f};
@@ -1492,7 +1455,7 @@ glu_status read_profile_impl(glu_radix_sort sort, double* count_ms, double* scan
         const uint8_t kind = p < sort->pass_kinds.size() ? sort->pass_kinds[p] : 0;
         const uint32_t seq = p < sort->pass_seqs.size() ? sort->pass_seqs[p] : 0u;
         // (this pass's sort: accepted?  ring entry = attempt number << 3 | tile geometry)
-        accepted = last_accepted;
+        bool accepted = last_accepted;
         if (seq && have_ring && (ring[seq & 255u] >> 3) == seq) accepted = (ring[seq & 255u] & 7u) != 0u;
         const bool attempted = seq != 0 || sort->last_finish_attempted;
         // (light profiling records no events around the sequence the host expects not to run: such a pass is not a live pass with
@@ -1523,44 +1486,37 @@ glu_status read_profile_impl(glu_radix_sort sort, double* count_ms, double* scan
     sort->slots.clear();
     sort->pass_kinds.clear();
     sort->pass_seqs.clear();
-    if (count_ms) *count_ms = acc[0];
-    if (scan_ms) *scan_ms = acc[1];
-    if (scatter_ms) *scatter_ms = acc[2];
-    if (passes) *passes = live;
-    if (finish_ms) *finish_ms = fin;
-    if (finish_passes) *finish_passes = fin_n;
+    store(count_ms, acc[0]);
+    store(scan_ms, acc[1]);
+    store(scatter_ms, acc[2]);
+    store(passes, live);
+    store(finish_ms, fin);
+    store(finish_passes, fin_n);
     return GLU_OK;
 }
-}
 
-glu_status glu_radix_sort_read_profile(glu_radix_sort sort, double* count_ms, double* scan_ms, double* scatter_ms,
-                                       uint64_t* passes)
+glu_status glu_radix_sort_read_profile(glu_radix_sort sort, double* count_ms, double* scan_ms, double* scatter_ms, uint64_t* passes)
 {
-    return read_profile_impl(sort, count_ms, scan_ms, scatter_ms, passes, nullptr, nullptr);
+    return glu_radix_sort_read_profile_finish(sort, count_ms, scan_ms, scatter_ms, passes, nullptr, nullptr);
 }
 
-glu_status glu_radix_sort_read_profile_finish(glu_radix_sort sort, double* count_ms, double* scan_ms, double* scatter_ms,
-                                              uint64_t* passes, double* finish_ms, uint64_t* finish_passes)
-{
-    return read_profile_impl(sort, count_ms, scan_ms, scatter_ms, passes, finish_ms, finish_passes);
-}
-
+// (the one entry point that does not ask for the device: it reads host fields only)
 glu_status glu_radix_sort_scratch_placement(glu_radix_sort sort, uint32_t* candidates, double* chosen_ms, double* slowest_ms)
 {
-    if (!sort) return fail(GLU_ERROR_INVALID_ARGUMENT, "sort is NULL");
-    if (candidates) *candidates = sort->tuned_candidates;
-    if (chosen_ms) *chosen_ms = sort->tuned_ms;
-    if (slowest_ms) *slowest_ms = sort->tuned_worst_ms;
+    GLU_TRY(check_not_null(sort, "sort"));
+    store(candidates, sort->tuned_candidates);
+    store(chosen_ms, sort->tuned_ms);
+    store(slowest_ms, sort->tuned_worst_ms);
     return GLU_OK;
 }
 
 glu_status glu_radix_sort_scratch_size(glu_radix_sort sort, size_t* bytes)
 {
     GLU_TRY(enter());
-    if (!sort || !bytes) return fail(GLU_ERROR_INVALID_ARGUMENT, "NULL argument");
-    *bytes = sort->keys.size + sort->vals.size + sort->table.size + sort->plan.size + sort->pair_t2.size + sort->pair_table.size +
-             sort->pair_ranges.size + sort->pair_sub.size + sort->seg_desc.size + sort->seg_zero.size + sort->finish_lengths.size +
-             sort->finish_starts.size + sort->seg_gate.size + sort->long_image.size + sort->long_hdr.size + sort->batch_lists.size;
+    GLU_TRY(check_none_null({sort, bytes}, "NULL argument"));
+    size_t sum = 0;
+    sort->for_each_scratch([&](const Scratch& sc) { sum += sc.size; });
+    store(bytes, sum);
     return GLU_OK;
 }
 

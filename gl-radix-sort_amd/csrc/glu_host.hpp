@@ -24,7 +24,7 @@
 // and top-k share tile_span.hpp (the tiles, the packs of an array at any alignment) on both sides; histogram and top-k share the counting
 // walk of histogram_walk.hpp.
 // The argument rules every unit checks by (key types, limits, overlap, alignment, items, handles, out-parameters) are glu_args.hpp's,
-// plain C++ that this header includes; the life of an operator object that owns only scratch is create_object / destroy_object below.
+// plain C++ that this header includes; the life of an operator object is create_object / destroy_object below, over its release().
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -119,8 +119,10 @@ struct Scratch
     }
 };
 
-// The life of an operator object T whose device memory is Scratch members: T::release() releases every one of them.
-// glu_*_create: `init` sets the new object up from the call's other arguments and may refuse them.
+// The life of an operator object T: T::release() gives back everything the object owns -- its Scratch members, and for the sort
+// object (glu_sort_object.hpp) its pinned host words, events and side stream as well.  The sharded sort keeps a life cycle of its
+// own (glu_dist_impl.hpp: it owns communicators).
+// glu_*_create: `init` sets the new object up from the call's other arguments, or from the environment, and may refuse them.
 template<typename T, typename Init>
 glu_status create_object(T** out, Init&& init)
 {

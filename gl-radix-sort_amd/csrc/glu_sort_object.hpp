@@ -255,6 +255,29 @@ struct glu_radix_sort_s
             if ((e = next_event()) != nullptr) (void) hipEventRecord(e, stream);
         slots.push_back(e);
     }
+    // Every Scratch member, once: what release() frees and glu_radix_sort_scratch_size sums.  A new one is added here and nowhere else.
+    template<typename F>
+    void for_each_scratch(F&& f)
+    {
+        for (Scratch* sc : {&keys, &vals, &table, &plan, &pair_t2, &pair_table, &pair_ranges, &pair_sub, &pair_wide, &seg_desc, &seg_zero, &batch_lists,
+                            &long_image, &long_hdr, &long_bits, &seg_gate, &finish_lengths, &finish_starts, &finish_crowded, &finish_outcomes})
+            f(*sc);
+    }
+    // everything the object owns (create_object / destroy_object of glu_host.hpp; the caller has drained the device)
+    void release()
+    {
+        for_each_scratch([](Scratch& sc) { sc.release(); });
+        if (finish_hint) (void) hipHostFree(finish_hint);
+        for (hipEvent_t e : {ev_fork, ev_unit, ev_fork2, ev_join})
+            if (e) (void) hipEventDestroy(e);
+        if (side) (void) hipStreamDestroy(side);
+        for (hipEvent_t e : events) (void) hipEventDestroy(e);
+        for (SegStage& st : seg_stage)
+        {
+            if (st.host) (void) hipHostFree(st.host);
+            if (st.copied) (void) hipEventDestroy(st.copied);
+        }
+    }
 };
 
 namespace glu_hip

@@ -174,6 +174,24 @@ int main()
     }
     g_text.clear();
     printf("null %d %d [%s]\n", (int) check_not_null(&g_text, "merge"), (int) check_not_null(nullptr, "merge"), g_text.c_str());
+    // several pointers under the caller's whole sentence: any NULL among them refuses, once, with that sentence and nothing added
+    const void* const here = &g_text;
+    const char* const sentence = "100%s / name is NULL"; // (not a format)
+    int before = g_fails;
+    const int none_null[5] = {(int) check_none_null({here}, sentence), (int) check_none_null({here, here, here}, sentence), (int) check_none_null({}, sentence),
+                              (int) check_none_null({(const void*) nullptr}, sentence), g_fails - before};
+    printf("none_null accepted %d %d %d refused %d fails %d [%s]\n", none_null[0], none_null[1], none_null[2], none_null[3], none_null[4], g_text.c_str());
+    for (int at = 0; at < 3; at++)
+    {
+        g_text.clear();
+        before = g_fails;
+        const glu_status st = check_none_null({at == 0 ? nullptr : here, at == 1 ? nullptr : here, at == 2 ? nullptr : here}, "NULL array");
+        printf("none_null at %d %d fails %d [%s]\n", at, (int) st, g_fails - before, g_text.c_str());
+    }
+    g_text.clear();
+    before = g_fails;
+    const glu_status all_null = check_none_null({nullptr, nullptr}, "NULL argument"); // (one refusal, not two)
+    printf("none_null all %d fails %d [%s]\n", (int) all_null, g_fails - before, g_text.c_str());
     uint32_t word = 7;
     size_t wide = 7;
     store(&word, (size_t) 9);
@@ -262,6 +280,8 @@ def test_key_types_items_limits_and_out_parameters(printed):
     assert lines(printed, "limit") == ["0 0 [] 0 []", "4294967295 0 [] 0 []",
                                        "4294967296 1 [max_out must be below 2^32 (got 4294967296)] 1 [select takes a count below 2^32 (got 4294967296)]"]
     assert lines(printed, "null") == ["0 1 [merge is NULL]"]
+    assert lines(printed, "none_null") == ["accepted 0 0 0 refused 1 fails 1 [100%s / name is NULL]", "at 0 1 fails 1 [NULL array]",
+                                           "at 1 1 fails 1 [NULL array]", "at 2 1 fails 1 [NULL array]", "all 1 fails 1 [NULL argument]"]
     assert lines(printed, "store") == ["9 11"]
 
 

@@ -1,9 +1,13 @@
 """What every operator refuses, and a few edge cases it accepts, held against a record: tests/golden/refusals.json holds the status,
 the whole message (glu_last_error) and, where the unit has one, what *_last reports afterwards, for every call of CASES below.  The
-record was written by record() from the library of the commit BEFORE the argument checks moved into csrc/glu_args.hpp and is never
-written again from the code under test: a check that changes its place in the order, its text or its status shows here.
+record is never written from the code under test: record() wrote every case up to scan_batch.* from the library of the commit BEFORE the
+argument checks moved into csrc/glu_args.hpp, and the radix_sort.* and dist.* cases (the sort's own entry points and the sharded sort's)
+from the library of the commit before THOSE entry points moved onto that layer.  A check that changes its place in the order, its text or
+its status shows here.  Not in the record: what glu_dist_create and glu_dist_unique_id refuse (both ask for RCCL first), and with them a
+NULL out-parameter beside a live glu_dist handle.
 
-CASES is one table.  Plan entry points need no device and run unmarked; everything that takes an object is marked gpu.  The arrays
+CASES is one table.  Plan entry points, and the few handle checks that come before the library asks for its device, need no device and
+run unmarked; everything else that takes an object is marked gpu.  The arrays
 are two 4 KiB device allocations A and B (zeroed); no message holds an address, no refused call launches a kernel.  The cases run in
 the table's order on one object per unit, so *_last after a refused call is what the accepted call before it left."""
 import ctypes
@@ -25,7 +29,7 @@ LAST = {"merge": ("glu_merge_last", 2), "sorted_search": ("glu_sorted_search_las
 CREATE = {"merge": ("glu_merge_create",), "sorted_search": ("glu_sorted_search_create",), "histogram": ("glu_histogram_create",),
           "expand": ("glu_expand_create",), "select": ("glu_select_create",), "key_runs": ("glu_key_runs_create",),
           "scan": ("glu_scan_create", UINT), "reduce": ("glu_reduce_create", UINT, 0), "scan_d": ("glu_scan_create", DOUBLE),
-          "sort": ("glu_radix_sort_create",)}
+          "sort": ("glu_radix_sort_create",), "radix_sort": ("glu_radix_sort_create",)}
 DESTROY = {"scan_d": "glu_scan_destroy", "sort": "glu_radix_sort_destroy"}
 
 
@@ -38,6 +42,12 @@ class Ctx:
         self.lo, self.hi = ctypes.c_uint32(0), ctypes.c_uint32(64)
         self.flo, self.fhi = ctypes.c_float(1.0), ctypes.c_float(0.0)
         self.tmp = ctypes.c_void_p()
+        self.word, self.size = ctypes.c_uint32(), ctypes.c_size_t()
+        # host arrays of the sharded sort's plan calls: two ranks' histograms, owners (good, one too large, one negative), outputs
+        self.hist = (ctypes.c_uint32 * 512)(*[1] * 512)
+        self.owner, self.owner_high, self.owner_negative = [(ctypes.c_int * 256)(*([0] * 128 + [1] * 128)) for _ in range(3)]
+        self.owner_high[3], self.owner_negative[255] = 2, -1
+        self.send, self.recv, self.cut = (ctypes.c_uint64 * 2)(), (ctypes.c_uint64 * 2)(), (ctypes.c_int * 18)()
 
     def h(self, unit):
         if unit not in self._h:
@@ -133,6 +143,41 @@ def _scan_off(c, h="scan", data=0, total=8, offsets=0, nseg=2):
     return (c.h(h) if h else None, p(data), total, None if offsets is None else c.B + offsets, nseg, None)
 
 
+def _sort_ptr(c, h="radix_sort", keys=0, vals=2048, count=16, tail=(0,)):
+    """a *_ptr sort on A: handle, keys, vals (False: the entry point takes none), count, `tail` (steps / key type / bits), stream"""
+    p = lambda off: None if off is None else c.A + off
+    return (c.h(h) if h else None, p(keys)) + (() if vals is False else (p(vals),)) + (count,) + tuple(tail) + (None,)
+
+
+def _sort_buf(c, h="radix_sort", keys="bufA", vals="bufA", count=16):
+    """a sort of buffer handles (a name: that buffer of c; a number: that handle)"""
+    b = lambda x: getattr(c, x) if isinstance(x, str) else x
+    return (c.h(h) if h else None, b(keys)) + (() if vals is False else (b(vals),)) + (count, 0)
+
+
+def _sort_part(c, h="radix_sort", sk=0, sv=1024, dk=2048, dv=3072, count=16, shift=24, bits=8):
+    p = lambda off: None if off is None else c.A + off
+    return (c.h(h) if h else None, p(sk), p(sv), p(dk), p(dv), count, shift, bits, None, None)
+
+
+def _pieces(begin, length, seg):
+    """the three piece arrays of a segmented sort (None: NULL)"""
+    arr = lambda t, v: None if v is None else (t * max(len(v), 1))(*v)
+    return arr(ctypes.c_uint64, begin), arr(ctypes.c_uint64, length), arr(ctypes.c_uint32, seg)
+
+
+def _sort_seg(c, h="radix_sort", ik=0, iv=1024, ok=2048, ov=3072, count=8, begin=(0, 4), length=(4, 4), seg=(0, 1), n=2, nseg=2, bits=32):
+    p = lambda off: None if off is None else c.A + off
+    return (c.h(h) if h else None, p(ik), p(iv), p(ok), p(ov), count) + _pieces(begin, length, seg) + (n, nseg, bits, None)
+
+
+def _plan_seg(c, begin=(0, 4), length=(4, 4), seg=(0, 1), n=2, nseg=2, nwg=4, cap=64, num=True):
+    """glu_radix_sort_plan_segments with room for `cap` sub-blocks (the outputs of a refused call are never written)"""
+    room = lambda t, k: (t * (min(k, 64) + 1))()
+    return _pieces(begin, length, seg) + (n, nseg, nwg, room(ctypes.c_uint32, 2 * cap), cap, room(ctypes.c_uint32, nwg), room(ctypes.c_uint32, nseg),
+                                          room(ctypes.c_uint64, nseg), c.ref(c.size) if num else None)
+
+
 def case(name, fn, args, gpu=True):
     return {"name": name, "fn": fn, "args": args, "gpu": gpu}
 
@@ -168,6 +213,15 @@ def HD(name, **kw):
 
 def EX(name, **kw):
     return case("expand.run." + name, "glu_expand_run_ptr", lambda c: _expand(c, **kw))
+
+
+def RS(entry, name, build=_sort_ptr, **kw):
+    return case("radix_sort.%s.%s" % (entry, name), "glu_radix_sort_" + entry, lambda c: build(c, **kw))
+
+
+def host(name, fn, args):
+    """a call that needs no device and has no out-parameter to make: `args` is the whole argument list"""
+    return case(name, fn, args, gpu=False)
 
 
 CASES = [
@@ -573,6 +627,275 @@ CASES = [
     case("scan_batch.offsets.data_align", "glu_scan_run_batch_offsets_ptr", lambda c: _scan_off(c, data=2)),
     case("scan_batch.offsets.data_align_double", "glu_scan_run_batch_offsets_ptr", lambda c: _scan_off(c, h="scan_d", data=4)),
     case("scan_batch.offsets.ok_total_0", "glu_scan_run_batch_offsets_ptr", lambda c: _scan_off(c, total=0, data=None)),
+    # ---- the sort's own entry points, on one object of their own
+    case("radix_sort.create.null", "glu_radix_sort_create", lambda c: (None,)),
+    case("radix_sort.destroy.null", "glu_radix_sort_destroy", lambda c: (None,)),
+    case("radix_sort.prepare.null", "glu_radix_sort_prepare", lambda c: (None, 16)),
+    case("radix_sort.prepare.ok_count_0", "glu_radix_sort_prepare", lambda c: (c.h("radix_sort"), 0)),
+    case("radix_sort.prepare.ok_count_1", "glu_radix_sort_prepare", lambda c: (c.h("radix_sort"), 1)),
+    case("radix_sort.prepare_u64.null", "glu_radix_sort_prepare_u64", lambda c: (None, 16)),
+    case("radix_sort.prepare_u64.ok_count_0", "glu_radix_sort_prepare_u64", lambda c: (c.h("radix_sort"), 0)),
+    case("radix_sort.prepare_ex.null", "glu_radix_sort_prepare_ex", lambda c: (None, 16, 4, 1)),
+    case("radix_sort.prepare_ex.null+key_bytes", "glu_radix_sort_prepare_ex", lambda c: (None, 16, 2, 1)),
+    case("radix_sort.prepare_ex.key_bytes", "glu_radix_sort_prepare_ex", lambda c: (c.h("radix_sort"), 16, 2, 1)),
+    case("radix_sort.prepare_ex.key_bytes_16", "glu_radix_sort_prepare_ex", lambda c: (c.h("radix_sort"), 16, 16, 0)),
+    case("radix_sort.prepare_ex.key_bytes_before_count_0", "glu_radix_sort_prepare_ex", lambda c: (c.h("radix_sort"), 0, 3, 1)),
+    case("radix_sort.prepare_ex.ok_count_0", "glu_radix_sort_prepare_ex", lambda c: (c.h("radix_sort"), 0, 8, 0)),
+    RS("run_ptr", "null", h=None),
+    RS("run_ptr", "null+keys_null", h=None, keys=None),
+    RS("run_ptr", "keys_null+vals_null", keys=None, vals=None),
+    RS("run_ptr", "keys_null", keys=None),
+    RS("run_ptr", "vals_null", vals=None),
+    RS("run_ptr", "vals_null+count", vals=None, count=T32),
+    RS("run_ptr", "count", count=T32),
+    RS("run_ptr", "count+align", count=T32, keys=2),
+    RS("run_ptr", "keys_align", keys=2),
+    RS("run_ptr", "vals_align", vals=2049),
+    RS("run_ptr", "ok_count_0", keys=None, vals=None, count=0),
+    RS("run_ptr", "ok_count_1_misaligned_not_looked_at", keys=2, count=1),
+    RS("run_u64_ptr", "null", h=None),
+    RS("run_u64_ptr", "null+keys_null", h=None, keys=None),
+    RS("run_u64_ptr", "keys_null+vals_null", keys=None, vals=None),
+    RS("run_u64_ptr", "vals_null", vals=None),
+    RS("run_u64_ptr", "count", count=T32),
+    RS("run_u64_ptr", "keys_align", keys=4),
+    RS("run_u64_ptr", "ok_count_0", keys=None, vals=None, count=0),
+    RS("run_keys_ptr", "null", h=None, vals=False),
+    RS("run_keys_ptr", "null+keys_null", h=None, keys=None, vals=False),
+    RS("run_keys_ptr", "keys_null", keys=None, vals=False),
+    RS("run_keys_ptr", "keys_null+count", keys=None, vals=False, count=T32),
+    RS("run_keys_ptr", "count", vals=False, count=T32),
+    RS("run_keys_ptr", "keys_align", keys=2, vals=False),
+    RS("run_keys_ptr", "ok_count_0", keys=None, vals=False, count=0),
+    RS("run_keys_u64_ptr", "null", h=None, vals=False),
+    RS("run_keys_u64_ptr", "null+keys_null", h=None, keys=None, vals=False),
+    RS("run_keys_u64_ptr", "keys_null", keys=None, vals=False),
+    RS("run_keys_u64_ptr", "count", vals=False, count=T32),
+    RS("run_keys_u64_ptr", "keys_align", keys=4, vals=False),
+    RS("run_keys_u64_ptr", "ok_count_0", keys=None, vals=False, count=0),
+    RS("run_typed_ptr", "null", h=None, tail=(U32,)),
+    RS("run_typed_ptr", "null+key_type", h=None, tail=(BAD_KEY,)),
+    RS("run_typed_ptr", "key_type", tail=(6,)),
+    RS("run_typed_ptr", "key_type_negative", tail=(-1,)),
+    RS("run_typed_ptr", "key_type_before_count_0", count=0, keys=None, tail=(BAD_KEY,)),
+    RS("run_typed_ptr", "key_type+keys_null", keys=None, tail=(BAD_KEY,)),
+    RS("run_typed_ptr", "keys_null", keys=None, tail=(F64,)),
+    RS("run_typed_ptr", "keys_null+count", keys=None, count=T32, tail=(I32,)),
+    RS("run_typed_ptr", "count", count=T32, tail=(F32,)),
+    RS("run_typed_ptr", "keys_align_u32", keys=2, tail=(I32,)),
+    RS("run_typed_ptr", "keys_align_u64", keys=4, tail=(I64,)),
+    RS("run_typed_ptr", "ok_count_0", keys=None, vals=None, count=0, tail=(F64,)),
+    RS("run_bit_range_ptr", "null", h=None, tail=(32, 0, 32)),
+    RS("run_bit_range_ptr", "null+key_bits", h=None, tail=(48, 0, 32)),
+    RS("run_bit_range_ptr", "key_bits", tail=(48, 0, 32)),
+    RS("run_bit_range_ptr", "key_bits+bit_range", tail=(16, 8, 4)),
+    RS("run_bit_range_ptr", "bit_range_order", tail=(32, 8, 4)),
+    RS("run_bit_range_ptr", "bit_range_end", tail=(32, 0, 33)),
+    RS("run_bit_range_ptr", "bit_range_end_64", tail=(64, 0, 65)),
+    RS("run_bit_range_ptr", "bit_range_before_count_0", count=0, keys=None, tail=(32, 0, 33)),
+    RS("run_bit_range_ptr", "bit_range+keys_null", keys=None, tail=(32, 8, 4)),
+    RS("run_bit_range_ptr", "keys_null", keys=None, tail=(64, 0, 64)),
+    RS("run_bit_range_ptr", "keys_null+count", keys=None, count=T32, tail=(32, 0, 32)),
+    RS("run_bit_range_ptr", "count", count=T32, tail=(32, 0, 32)),
+    RS("run_bit_range_ptr", "keys_align_64", keys=4, tail=(64, 0, 64)),
+    RS("run_bit_range_ptr", "ok_count_0", keys=None, vals=None, count=0, tail=(32, 0, 32)),
+    RS("run_bit_range_ptr", "ok_no_bits_misaligned_not_looked_at", keys=2, tail=(32, 8, 8)),
+    RS("run", "null", _sort_buf, h=None),
+    RS("run", "null+key_buffer", _sort_buf, h=None, keys=0),
+    RS("run", "key_buffer+value_buffer", _sort_buf, keys=0, vals=0),
+    RS("run", "key_buffer", _sort_buf, keys=0),
+    RS("run", "key_buffer_unknown", _sort_buf, keys=0x7FFFFFF0),
+    RS("run", "value_buffer", _sort_buf, vals=0),
+    RS("run", "value_buffer+size", _sort_buf, vals=0, count=1025),
+    RS("run", "value_buffer_unknown", _sort_buf, vals=0x7FFFFFF0),
+    RS("run", "size", _sort_buf, count=1025),
+    RS("run", "size+count", _sort_buf, count=T32),
+    RS("run", "ok_count_0", _sort_buf, count=0),
+    RS("run", "ok_count_1", _sort_buf, count=1),
+    RS("run_u64", "null", _sort_buf, h=None),
+    RS("run_u64", "key_buffer+value_buffer", _sort_buf, keys=0, vals=0),
+    RS("run_u64", "value_buffer", _sort_buf, vals=0),
+    RS("run_u64", "size_keys", _sort_buf, count=513),
+    RS("run_u64", "ok_count_0", _sort_buf, count=0),
+    RS("run_keys", "null", _sort_buf, h=None, vals=False),
+    RS("run_keys", "null+key_buffer", _sort_buf, h=None, keys=0, vals=False),
+    RS("run_keys", "key_buffer", _sort_buf, keys=0, vals=False),
+    RS("run_keys", "size", _sort_buf, vals=False, count=1025),
+    RS("run_keys", "ok_count_0", _sort_buf, vals=False, count=0),
+    RS("partition_ptr", "null", _sort_part, h=None),
+    RS("partition_ptr", "null+null_array", _sort_part, h=None, sk=None),
+    RS("partition_ptr", "src_keys_null", _sort_part, sk=None),
+    RS("partition_ptr", "src_vals_null", _sort_part, sv=None),
+    RS("partition_ptr", "dst_keys_null", _sort_part, dk=None),
+    RS("partition_ptr", "dst_vals_null", _sort_part, dv=None),
+    RS("partition_ptr", "null_array+same", _sort_part, sv=None, sk=2048),
+    RS("partition_ptr", "same_keys", _sort_part, dk=0),
+    RS("partition_ptr", "same_vals", _sort_part, dv=1024),
+    RS("partition_ptr", "same+digit", _sort_part, dk=0, bits=0),
+    RS("partition_ptr", "digit_bits_0", _sort_part, bits=0),
+    RS("partition_ptr", "digit_bits_9", _sort_part, shift=0, bits=9),
+    RS("partition_ptr", "digit_past_32", _sort_part, shift=28, bits=8),
+    RS("partition_ptr", "digit_before_count_0", _sort_part, sk=None, sv=None, dk=None, dv=None, count=0, bits=0),
+    RS("partition_ptr", "digit+count", _sort_part, bits=0, count=T32),
+    RS("partition_ptr", "count", _sort_part, count=T32),
+    RS("partition_ptr", "ok_count_0", _sort_part, sk=None, sv=None, dk=None, dv=None, count=0),
+    RS("run_segments_ptr", "null", _sort_seg, h=None),
+    RS("run_segments_ptr", "null+key_bits", _sort_seg, h=None, bits=12),
+    RS("run_segments_ptr", "key_bits_12", _sort_seg, bits=12),
+    RS("run_segments_ptr", "key_bits_40", _sort_seg, bits=40),
+    RS("run_segments_ptr", "key_bits+count", _sort_seg, bits=12, count=T32),
+    RS("run_segments_ptr", "count", _sort_seg, count=T32),
+    RS("run_segments_ptr", "count+pieces_null", _sort_seg, count=T32, begin=None),
+    RS("run_segments_ptr", "piece_begin_null", _sort_seg, begin=None),
+    RS("run_segments_ptr", "piece_len_null", _sort_seg, length=None),
+    RS("run_segments_ptr", "piece_segment_null", _sort_seg, seg=None),
+    RS("run_segments_ptr", "pieces_null+no_segments", _sort_seg, seg=None, nseg=0),
+    RS("run_segments_ptr", "no_segments", _sort_seg, nseg=0),
+    RS("run_segments_ptr", "segments_max", _sort_seg, nseg=(1 << 24) + 1),
+    RS("run_segments_ptr", "segments_max+piece_overruns", _sort_seg, nseg=(1 << 24) + 1, begin=(0, 9)),
+    RS("run_segments_ptr", "piece_segment", _sort_seg, seg=(0, 2)),
+    RS("run_segments_ptr", "piece_segment+piece_overruns", _sort_seg, seg=(2, 0), begin=(9, 4)),
+    RS("run_segments_ptr", "piece_overruns_then_piece_segment", _sort_seg, seg=(0, 2), begin=(9, 4)),
+    RS("run_segments_ptr", "piece_begin_overruns", _sort_seg, begin=(0, 9)),
+    RS("run_segments_ptr", "piece_len_overruns", _sort_seg, length=(4, 5)),
+    RS("run_segments_ptr", "piece_overruns+total", _sort_seg, length=(2, 9)),
+    RS("run_segments_ptr", "total_short", _sort_seg, length=(4, 3)),
+    RS("run_segments_ptr", "total_long", _sort_seg, begin=(0, 0), length=(4, 8)),
+    RS("run_segments_ptr", "total_of_no_pieces", _sort_seg, n=0, begin=None, length=None, seg=None),
+    RS("run_segments_ptr", "total+tile", _sort_seg, begin=(0, 0), length=(4, 3)),
+    RS("run_segments_ptr", "tile_twice", _sort_seg, begin=(0, 0)),
+    RS("run_segments_ptr", "tile_gap", _sort_seg, count=6, begin=(0, 4, 4), length=(2, 2, 2), seg=(0, 1, 1), n=3),
+    RS("run_segments_ptr", "tile+null_array", _sort_seg, begin=(0, 0), ik=None),
+    RS("run_segments_ptr", "in_keys_null", _sort_seg, ik=None),
+    RS("run_segments_ptr", "in_vals_null", _sort_seg, iv=None),
+    RS("run_segments_ptr", "out_keys_null", _sort_seg, ok=None),
+    RS("run_segments_ptr", "out_vals_null", _sort_seg, ov=None),
+    RS("run_segments_ptr", "null_array+same", _sort_seg, iv=None, ok=0),
+    RS("run_segments_ptr", "same_keys", _sort_seg, ok=0),
+    RS("run_segments_ptr", "same_vals", _sort_seg, ov=1024),
+    RS("run_segments_ptr", "ok_count_0", _sort_seg, ik=None, iv=None, ok=None, ov=None, count=0, n=0, begin=None, length=None, seg=None, nseg=0),
+    RS("run_segments_ptr", "empty_piece_past_count_0", _sort_seg, ik=None, iv=None, ok=None, ov=None, count=0, length=(0, 0)),
+    case("radix_sort.set_digit_bits.null", "glu_radix_sort_set_digit_bits", lambda c: (None, 8)),
+    case("radix_sort.set_digit_bits.null+bits", "glu_radix_sort_set_digit_bits", lambda c: (None, 5)),
+    case("radix_sort.set_digit_bits.bits_5", "glu_radix_sort_set_digit_bits", lambda c: (c.h("radix_sort"), 5)),
+    case("radix_sort.set_digit_bits.bits_0", "glu_radix_sort_set_digit_bits", lambda c: (c.h("radix_sort"), 0)),
+    case("radix_sort.set_digit_bits.ok_4", "glu_radix_sort_set_digit_bits", lambda c: (c.h("radix_sort"), 4)),
+    case("radix_sort.set_digit_bits.ok_8", "glu_radix_sort_set_digit_bits", lambda c: (c.h("radix_sort"), 8)),
+    case("radix_sort.get_digit_bits.null", "glu_radix_sort_get_digit_bits", lambda c: (None, c.ref(c.word))),
+    case("radix_sort.get_digit_bits.null+bits_null", "glu_radix_sort_get_digit_bits", lambda c: (None, None)),
+    case("radix_sort.get_digit_bits.bits_null", "glu_radix_sort_get_digit_bits", lambda c: (c.h("radix_sort"), None)),
+    case("radix_sort.get_digit_bits.ok", "glu_radix_sort_get_digit_bits", lambda c: (c.h("radix_sort"), c.ref(c.word))),
+    case("radix_sort.set_option.null", "glu_radix_sort_set_option", lambda c: (None, b"SORT_NO_PLAN", 0)),
+    case("radix_sort.set_option.null+name_null", "glu_radix_sort_set_option", lambda c: (None, None, 0)),
+    case("radix_sort.set_option.name_null", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), None, 0)),
+    case("radix_sort.set_option.unknown", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"SORT_FASTER", 1)),
+    case("radix_sort.set_option.unknown_prefix_only", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"GLU_HIP_", 1)),
+    case("radix_sort.set_option.unknown_empty", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"", 1)),
+    case("radix_sort.set_option.ok", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"SORT_NO_PLAN", 0)),
+    case("radix_sort.set_option.ok_environment_spelling", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"glu_hip_sort_no_plan", 0)),
+    case("radix_sort.set_option.ok_digit_bits_5_ignored", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"DIGIT_BITS", 5)),
+    case("radix_sort.set_option.ok_sort_blocks_negative_ignored", "glu_radix_sort_set_option", lambda c: (c.h("radix_sort"), b"SORT_BLOCKS", -1)),
+    case("radix_sort.scratch_size.null", "glu_radix_sort_scratch_size", lambda c: (None, c.ref(c.size))),
+    case("radix_sort.scratch_size.null+bytes_null", "glu_radix_sort_scratch_size", lambda c: (None, None)),
+    case("radix_sort.scratch_size.bytes_null", "glu_radix_sort_scratch_size", lambda c: (c.h("radix_sort"), None)),
+    case("radix_sort.scratch_size.ok", "glu_radix_sort_scratch_size", lambda c: (c.h("radix_sort"), c.ref(c.size))),
+    host("radix_sort.scratch_placement.null", "glu_radix_sort_scratch_placement", lambda c: (None, None, None, None)),
+    case("radix_sort.scratch_placement.ok_outs_null", "glu_radix_sort_scratch_placement", lambda c: (c.h("radix_sort"), None, None, None)),
+    case("radix_sort.read_plan.null", "glu_radix_sort_read_plan", lambda c: (None, None, None, None, 4)),
+    case("radix_sort.read_plan.null+passes", "glu_radix_sort_read_plan", lambda c: (None, None, None, None, 33)),
+    case("radix_sort.read_plan.passes+no_sort", "glu_radix_sort_read_plan", lambda c: (c.h("radix_sort"), None, None, None, 33)),
+    case("radix_sort.read_plan.no_sort", "glu_radix_sort_read_plan", lambda c: (c.h("radix_sort"), None, None, None, 32)),
+    case("radix_sort.read_plan.no_sort_no_passes", "glu_radix_sort_read_plan", lambda c: (c.h("radix_sort"), None, None, None, 0)),
+    case("radix_sort.read_finish.null", "glu_radix_sort_read_finish", lambda c: (None,) * 6),
+    case("radix_sort.read_finish.ok_no_sort", "glu_radix_sort_read_finish", lambda c: (c.h("radix_sort"),) + (None,) * 5),
+    case("radix_sort.read_long_runs.null", "glu_radix_sort_read_long_runs", lambda c: (None,) * 4),
+    case("radix_sort.read_long_runs.ok_no_sort", "glu_radix_sort_read_long_runs", lambda c: (c.h("radix_sort"),) + (None,) * 3),
+    case("radix_sort.read_seg_finish.null", "glu_radix_sort_read_seg_finish", lambda c: (None,) * 8),
+    case("radix_sort.read_seg_finish.ok_no_sort", "glu_radix_sort_read_seg_finish", lambda c: (c.h("radix_sort"),) + (None,) * 7),
+    case("radix_sort.read_profile.null", "glu_radix_sort_read_profile", lambda c: (None,) * 5),
+    case("radix_sort.read_profile.ok_no_sort", "glu_radix_sort_read_profile", lambda c: (c.h("radix_sort"),) + (None,) * 4),
+    case("radix_sort.read_profile_finish.null", "glu_radix_sort_read_profile_finish", lambda c: (None,) * 7),
+    case("radix_sort.read_profile_finish.ok_no_sort", "glu_radix_sort_read_profile_finish", lambda c: (c.h("radix_sort"),) + (None,) * 6),
+    case("radix_sort.set_profiling.null", "glu_radix_sort_set_profiling", lambda c: (None, 1)),
+    case("radix_sort.set_profiling.ok_off", "glu_radix_sort_set_profiling", lambda c: (c.h("radix_sort"), 0)),
+    # ---- the sort's plan entry points
+    plan("radix_sort.plan_finish.key_bytes", "glu_radix_sort_plan_finish", 1 << 28, 2),
+    plan("radix_sort.plan_finish.key_bytes_before_count_0", "glu_radix_sort_plan_finish", 0, 16),
+    plan("radix_sort.plan_finish.ok", "glu_radix_sort_plan_finish", 1 << 28, 4),
+    plan("radix_sort.plan_finish.ok_wide", "glu_radix_sort_plan_finish", 1 << 24, 8),
+    plan("radix_sort.plan_finish.ok_no_attempt", "glu_radix_sort_plan_finish", 1 << 20, 4),
+    plan("radix_sort.plan_finish.ok_count_0", "glu_radix_sort_plan_finish", 0, 4),
+    host("radix_sort.plan_segments.piece_begin_null", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, begin=None)),
+    host("radix_sort.plan_segments.piece_len_null", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, length=None)),
+    host("radix_sort.plan_segments.piece_segment_null", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, seg=None)),
+    host("radix_sort.plan_segments.pieces_null+workgroups_0", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, seg=None, nwg=0)),
+    host("radix_sort.plan_segments.workgroups_0", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, nwg=0)),
+    host("radix_sort.plan_segments.num_sub_blocks_null", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, num=False)),
+    host("radix_sort.plan_segments.workgroups_0+segments_max", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, nwg=0, nseg=(1 << 24) + 1)),
+    host("radix_sort.plan_segments.segments_max", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, nseg=(1 << 24) + 1)),
+    host("radix_sort.plan_segments.segments_max+workgroups_max", "glu_radix_sort_plan_segments",
+         lambda c: _plan_seg(c, nseg=(1 << 24) + 1, nwg=(1 << 20) + 1)),
+    host("radix_sort.plan_segments.workgroups_max", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, nwg=(1 << 20) + 1)),
+    host("radix_sort.plan_segments.workgroups_max+piece_segment", "glu_radix_sort_plan_segments",
+         lambda c: _plan_seg(c, nwg=(1 << 20) + 1, seg=(0, 2))),
+    host("radix_sort.plan_segments.piece_segment", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, seg=(0, 2))),
+    host("radix_sort.plan_segments.no_segments", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, nseg=0)),
+    host("radix_sort.plan_segments.piece_segment+total", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, seg=(2, 0), length=(0xFFFF0000, 1))),
+    host("radix_sort.plan_segments.total", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, length=(0xFFFF0000, 1))),
+    host("radix_sort.plan_segments.room", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, cap=0)),
+    host("radix_sort.plan_segments.ok", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c)),
+    host("radix_sort.plan_segments.ok_pieces_overlap_not_looked_at", "glu_radix_sort_plan_segments", lambda c: _plan_seg(c, begin=(0, 0))),
+    host("radix_sort.plan_segments.ok_no_pieces", "glu_radix_sort_plan_segments",
+         lambda c: _plan_seg(c, n=0, begin=None, length=None, seg=None, nseg=0)),
+    # ---- the sharded sort: its plan calls, and every handle check (no object: making one needs RCCL)
+    host("dist.plan_buckets.hist_null", "glu_dist_plan_buckets", lambda c: (None, 2, c.owner)),
+    host("dist.plan_buckets.owner_null", "glu_dist_plan_buckets", lambda c: (c.hist, 2, None)),
+    host("dist.plan_buckets.world_0", "glu_dist_plan_buckets", lambda c: (c.hist, 0, c.owner)),
+    host("dist.plan_buckets.ok", "glu_dist_plan_buckets", lambda c: (c.hist, 2, c.owner)),
+    host("dist.plan_counts.hist_null", "glu_dist_plan_counts", lambda c: (None, 2, 0, c.owner, c.send, c.recv)),
+    host("dist.plan_counts.owner_null", "glu_dist_plan_counts", lambda c: (c.hist, 2, 0, None, c.send, c.recv)),
+    host("dist.plan_counts.send_null", "glu_dist_plan_counts", lambda c: (c.hist, 2, 0, c.owner, None, c.recv)),
+    host("dist.plan_counts.recv_null", "glu_dist_plan_counts", lambda c: (c.hist, 2, 0, c.owner, c.send, None)),
+    host("dist.plan_counts.world_0", "glu_dist_plan_counts", lambda c: (c.hist, 0, 0, c.owner, c.send, c.recv)),
+    host("dist.plan_counts.rank_negative", "glu_dist_plan_counts", lambda c: (c.hist, 2, -1, c.owner, c.send, c.recv)),
+    host("dist.plan_counts.rank_is_world", "glu_dist_plan_counts", lambda c: (c.hist, 2, 2, c.owner, c.send, c.recv)),
+    host("dist.plan_counts.rank+owner", "glu_dist_plan_counts", lambda c: (c.hist, 2, 2, c.owner_high, c.send, c.recv)),
+    host("dist.plan_counts.owner_high", "glu_dist_plan_counts", lambda c: (c.hist, 2, 1, c.owner_high, c.send, c.recv)),
+    host("dist.plan_counts.owner_negative", "glu_dist_plan_counts", lambda c: (c.hist, 2, 1, c.owner_negative, c.send, c.recv)),
+    host("dist.plan_counts.owner_is_world", "glu_dist_plan_counts", lambda c: (c.hist, 1, 0, c.owner, c.send, c.recv)),
+    host("dist.plan_counts.ok", "glu_dist_plan_counts", lambda c: (c.hist, 2, 1, c.owner, c.send, c.recv)),
+    host("dist.plan_groups.hist_null", "glu_dist_plan_groups", lambda c: (None, 2, c.owner, 2, c.cut)),
+    host("dist.plan_groups.owner_null", "glu_dist_plan_groups", lambda c: (c.hist, 2, None, 2, c.cut)),
+    host("dist.plan_groups.cut_null", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner, 2, None)),
+    host("dist.plan_groups.world_0", "glu_dist_plan_groups", lambda c: (c.hist, 0, c.owner, 2, c.cut)),
+    host("dist.plan_groups.rounds_0", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner, 0, c.cut)),
+    host("dist.plan_groups.rounds_9", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner, 9, c.cut)),
+    host("dist.plan_groups.rounds+owner", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner_high, 9, c.cut)),
+    host("dist.plan_groups.owner_high", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner_high, 2, c.cut)),
+    host("dist.plan_groups.owner_negative", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner_negative, 8, c.cut)),
+    host("dist.plan_groups.ok", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner, 2, c.cut)),
+    host("dist.plan_groups.ok_rounds_8", "glu_dist_plan_groups", lambda c: (c.hist, 2, c.owner, 8, c.cut)),
+    host("dist.destroy.null", "glu_dist_destroy", lambda c: (None,)),
+    host("dist.partition_shift.null", "glu_dist_partition_shift", lambda c: (None, c.ref(c.word))),
+    host("dist.partition_shift.null+shift_null", "glu_dist_partition_shift", lambda c: (None, None)),
+    host("dist.world.null", "glu_dist_world", lambda c: (None, None, None)),
+    host("dist.local_sorter.null", "glu_dist_local_sorter", lambda c: (None, c.ref(c.tmp))),
+    host("dist.local_sorter.null+out_null", "glu_dist_local_sorter", lambda c: (None, None)),
+    host("dist.set_profiling.null", "glu_dist_set_profiling", lambda c: (None, 1)),
+    host("dist.set_rounds.null", "glu_dist_set_rounds", lambda c: (None, 2)),
+    host("dist.set_rounds.null+rounds", "glu_dist_set_rounds", lambda c: (None, 9)),
+    host("dist.last_rounds.null", "glu_dist_last_rounds", lambda c: (None, c.ref(c.word))),
+    host("dist.last_rounds.null+rounds_null", "glu_dist_last_rounds", lambda c: (None, None)),
+    host("dist.last_local_sort.null", "glu_dist_last_local_sort", lambda c: (None, c.ref(c.word))),
+    host("dist.last_local_sort.null+segmented_null", "glu_dist_last_local_sort", lambda c: (None, None)),
+    case("dist.prepare.null", "glu_dist_prepare", lambda c: (None, 16, 16)),
+    case("dist.set_reserved_cus.null", "glu_dist_set_reserved_cus", lambda c: (None, 8)),
+    case("dist.set_reserved_cus.null+cus", "glu_dist_set_reserved_cus", lambda c: (None, -1)),
+    case("dist.phase_times.null", "glu_dist_phase_times", lambda c: (None, None, None)),
+    case("dist.sort_begin.null", "glu_dist_sort_begin", lambda c: (None, c.A, c.A + 2048, 16, None, c.ref(c.size))),
+    case("dist.sort_begin.null+arrays_null", "glu_dist_sort_begin", lambda c: (None, None, None, 16, None, None)),
+    case("dist.sort_finish.null", "glu_dist_sort_finish", lambda c: (None, c.A, c.A + 2048, 16, None)),
+    case("dist.sort_ptr.null", "glu_dist_sort_ptr", lambda c: (None, c.A, c.A + 2048, 16, None, None, None, None)),
 ]
 
 
