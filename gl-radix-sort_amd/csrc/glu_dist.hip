@@ -1,5 +1,6 @@
-// glu_dist_impl.hpp -- the sharded (multi-GPU) radix sort behind the glu_dist_* entry points of include/glu_hip.h.
-// Included by glu_hip.hip (same translation unit: it uses the library's pass launchers and scratch objects).
+// glu_dist.hip -- the sharded (multi-GPU) radix sort behind the glu_dist_* entry points of include/glu_hip.h.
+// It defines no kernels: it reaches the sort through glu_sort_driver.hpp, dispatch_pass (glu_sort_object.hpp) and the public
+// glu_radix_sort_create / _destroy.
 //
 // The reference is single-device (replicas only); BASELINE.json configs[3] asks for the
 // sharded form: rank r holds slice r of the array, one exchange step on the top 8 key bits, then local sorts.
@@ -26,10 +27,24 @@
 // bucket has one owner, the partition and the local sort are stable, and receive segments keep (source rank, source
 // index) order.  RCCL is bound with dlopen at first use, so the library has no link-time dependency on it and a process
 // that already carries a librccl (PyTorch's) keeps using that one.
-#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
+
+#include "glu_host.hpp"
+#include "glu_sort_driver.hpp"
+
+using namespace glu_hip;
+using namespace glu_hip::host;
 
 namespace
 {

@@ -1,9 +1,14 @@
 // glu_host.hpp -- what the translation units of libglu_hip.so share on the HOST side: the error slot behind glu_last_error(), the
 // one device of the process and its queue, the buffer registry behind the glu_buffer handles, grow-only scratch allocations.
-// Defined in glu_core.hip.  The library is built from sixteen translation units (round 6; it was one, a three-minute compile):
+// Defined in glu_core.hip.  The library is built from twenty-one translation units (it was one, a three-minute compile):
 //   glu_core.hip              errors, device, buffers, timer
-//   glu_hip.hip               RadixSort's launch sequences (what a call decides before it enqueues: sort_call_plan.hpp, plain C++), the
-//                             placement search, the segmented sort and the sharded sort (glu_dist_impl.hpp)
+//   glu_hip.hip               RadixSort's whole-key driver: sort_prepare, sort_bits (what a call decides before it enqueues:
+//                             sort_call_plan.hpp, plain C++), the options and the entry points that are not about segments or placement
+//   glu_sort_placement.hip    the placement search: large scratch arrays placed by measurement
+//   glu_sort_segments.hip     the segmented passes (long runs of a whole-key sort) and the segmented sort (its host arithmetic:
+//                             seg_plan.hpp, plain C++)
+//   glu_dist.hip              the sharded sort (glu_dist_*); no kernels of its own
+//                             (these four and the batched sort call one another through glu_sort_driver.hpp)
 //   glu_sort_passes_u32.hip   the launchers of one counting pass for 4-byte keys (glu_sort_passes.hpp over glu_sort_object.hpp)
 //   glu_sort_passes_u64.hip   the same for 8-byte keys
 //   glu_sort_finish.hip       the launches of the in-LDS pass (radix_lds_bucket.hpp, radix_lds_finish.hpp: a hundred kernel instantiations)
@@ -19,6 +24,7 @@
 //   glu_expand.hip            expand: segment, rank and item per element from the offsets (expand_kernels.hpp over expand_path.hpp)
 //   glu_gather.hip            gather and scatter: items fetched or placed by device indices (gather_kernels.hpp over gather_walk.hpp)
 //   glu_top_k.hip             top-k: the k smallest or largest keys and their indices by a radix select (topk_kernels.hpp over topk_pick.hpp)
+//   glu_top_k_batch.hip       batched top-k: the k best keys of every segment in one call (topk_batch_kernels.hpp over topk_batch_plan.hpp)
 // The three batched units share glu_batch_host.hpp on the host side and batch_lists.hpp (the segment lists) on both sides.
 // Key runs, select, sorted search, merge, histogram, expand and top-k share glu_tile_host.hpp on the host side; the first three, histogram
 // and top-k share tile_span.hpp (the tiles, the packs of an array at any alignment) on both sides; histogram and top-k share the counting
@@ -121,7 +127,7 @@ struct Scratch
 
 // The life of an operator object T: T::release() gives back everything the object owns -- its Scratch members, and for the sort
 // object (glu_sort_object.hpp) its pinned host words, events and side stream as well.  The sharded sort keeps a life cycle of its
-// own (glu_dist_impl.hpp: it owns communicators).
+// own (glu_dist.hip: it owns communicators).
 // glu_*_create: `init` sets the new object up from the call's other arguments, or from the environment, and may refuse them.
 template<typename T, typename Init>
 glu_status create_object(T** out, Init&& init)

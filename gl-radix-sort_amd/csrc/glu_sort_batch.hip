@@ -7,7 +7,7 @@
 #include <mutex>
 
 #include "glu_batch_host.hpp"
-#include "glu_sort_object.hpp"
+#include "glu_sort_driver.hpp"
 #include "radix_batch_kernels.hpp"
 
 using namespace glu_hip;
@@ -140,7 +140,7 @@ glu_status run_offsets(glu_radix_sort_s* s, KeyT* keys, uint32_t* vals, size_t t
                        uint32_t xf, hipStream_t stream)
 {
     // the long class sorts between the caller's arrays and the object's scratch arrays
-    GLU_TRY(sort_prepare_plain(s, total, sizeof(KeyT), VALS));
+    GLU_TRY(sort_prepare(s, total, sizeof(KeyT), VALS, false));
     BatchArgs a;
     a.offsets = offsets;
     a.total = (uint32_t) total;

@@ -1,4 +1,4 @@
-// glu_sort_launch.hpp -- the launches of the in-LDS pass (defined in glu_sort_finish.hip, called from glu_hip.hip): a translation
+// glu_sort_launch.hpp -- the launches of the in-LDS pass (defined in glu_sort_finish.hip, called from glu_hip.hip and glu_sort_segments.hip): a translation
 // unit of their own because radix_finish_bucket_kernel and radix_finish_sort_kernel are a hundred instantiations.
 #pragma once
 #include <cmath>
@@ -31,7 +31,7 @@ inline uint32_t finish_rank_from(uint32_t low_bits, uint32_t rank_bits)
 
 // The two profile marks of the in-LDS pass go around the launch of the EXPECTED tile, the one that does the work in a timed
 // loop -- not around the launches beside it that return at once (glu_radix_sort_s::mark, through this pair: the sort object's
-// type stays in glu_hip.hip).
+// type stays out of glu_sort_finish.hip).
 struct FinishMarks
 {
     void (*mark)(void* object, hipStream_t stream) = nullptr;
@@ -42,7 +42,7 @@ struct FinishMarks
     }
 };
 
-// The in-LDS pass of a segmented sort, src -> dst over `nruns` runs (seg_run_plan): tile geometry `geo` (1 .. 4); split_log2 = 0: a
+// The in-LDS pass of a segmented sort, src -> dst over `nruns` runs (glu_sort_segments.hip: seg_run_plan): tile geometry `geo` (1 .. 4); split_log2 = 0: a
 // workgroup per run for the runs that fit the tile and radix_finish_ranges_kernel behind it for the longer ones; split_log2 > 0:
 // every run is split over 2^split_log2 workgroups of the ranges kernel.  Both return at once if the longest run (*gate) is
 // beyond gate_cap.

@@ -1,6 +1,7 @@
 // glu_sort_object.hpp -- the sort object (glu_radix_sort_s), the launch geometries and the arguments of a planned pass: what
-// glu_hip.hip (RadixSort's launch sequences) and glu_sort_passes.hpp (the launchers of one counting pass, compiled per key width
-// in glu_sort_passes_u32.hip / _u64.hip: 190 kernel instantiations) share.
+// the sort's units (glu_hip.hip, glu_sort_placement.hip, glu_sort_segments.hip, glu_sort_batch.hip, glu_dist.hip) and
+// glu_sort_passes.hpp (the launchers of one counting pass, compiled per key width in glu_sort_passes_u32.hip / _u64.hip: 190 kernel
+// instantiations) share.  What those units call in one another: glu_sort_driver.hpp.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -366,13 +367,6 @@ bool lines_applicable(const glu_radix_sort_s* s, const void* src_k, const void* 
     // (at least one whole tile: the kernel's branch-free prefetch reads tile 0 when it has nothing better to read)
     return aligned && !s->no_lines && !s->force_small && count >= lines_tile && count >= large_tiles_from<KeyT, BITS>(s, vals, lines_tile);
 }
-
-// The lazy scratch allocation at the head of a sort (glu_hip.hip: sort_prepare without the placement search), for the batched sort's
-// translation unit.
-glu_status sort_prepare_plain(glu_radix_sort_s* s, size_t count, size_t key_size, bool with_vals);
-// glu_radix_sort_run_typed_ptr's sort with every launch on `stream` itself: no part of the launch sequence may go to the object's side
-// stream (glu_hip.hip, beside the one place that forks).  The batched sort loops it over partitions longer than an LDS tile.
-glu_status sort_typed_one_queue(glu_radix_sort_s* s, void* keys, uint32_t* vals, size_t count, glu_key_type key_type, hipStream_t stream);
 
 // One counting pass (count -> row scan -> scatter, or the leader / follower of a pair of passes), 4- or 8-bit digits, the geometry
 // by size: glu_sort_passes.hpp, instantiated for 4-byte keys in glu_sort_passes_u32.hip and for 8-byte keys in _u64.hip.

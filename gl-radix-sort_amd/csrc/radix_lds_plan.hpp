@@ -7,7 +7,7 @@
 //   radix_finish_long_runs_kernel the runs longer than the chosen tile, as segments of segmented passes
 //
 // Launched from glu_sort_passes.hpp (the kernels that are not templates are `static`: both of its translation units hold a copy);
-// glu_hip.hip takes the sample kernel and the layout of the long runs from here; the kernels of the in-LDS pass itself are launched
+// glu_hip.hip takes the sample kernel and glu_sort_segments.hip the layout of the long runs from here; the kernels of the in-LDS pass itself are launched
 // from glu_sort_finish.hip.
 #pragma once
 
@@ -124,7 +124,7 @@ constexpr uint32_t kLongRunsMinShare = 4096;  // pairs: the least one workgroup 
 constexpr uint32_t kLongRunsSharesPerWg = 8;
 
 // The runs longer than the tile the plan chose, as SEGMENTS of segmented passes (radix_seg_passes.hpp): the descriptor image
-// the host builds for the sharded sort's local sort (seg_build_image in glu_hip.hip), built on the device from the run starts.
+// the host builds for the sharded sort's local sort (seg_build_image in seg_plan.hpp), built on the device from the run starts.
 // The long runs laid end to end are cut into nwg equal shares, a sub-block is the part of one run inside one share:
 //   image + 0:          subs[kLongRunsMax + nwg] (begin, end) element ranges, in the order of the runs  (nwg here and below: the number
 //                       of SHARES, kLongRunsSharesPerWg times the number of workgroups of the segmented passes)

@@ -84,7 +84,7 @@ struct LineSmem
 // (0.75-0.77 ms on a fast device either way, 0.912 -> 0.89 ms on a slow one, no difference inside the sort on five devices:
 // DESIGN.md section 4.2) -- the kernel is not bound by its instruction issue, so the undocumented order is not relied upon.
 //
-// SEG (segmented passes: the local sort of the sharded sort, glu_dist_impl.hpp): the workgroup runs the whole pass body once
+// SEG (segmented passes: the local sort of the sharded sort, glu_dist.hip over glu_sort_segments.hip): the workgroup runs the whole pass body once
 // per SUB-BLOCK of its list [seg_first[b], seg_first[b + 1]): element range `ranges[i]` of the source arrays, counted on its
 // own (radix_seg_count_kernel), with `table[i * RADIX + d]` = the ABSOLUTE destination index of the sub-block's first
 // element with digit d (radix_seg_scan_kernel: segment start + digits below d in the segment + the segment's earlier

@@ -1,12 +1,12 @@
 // radix_seg_passes.hpp -- count and scan kernels of SEGMENTED counting passes (glu_radix_sort_run_segments_ptr: the local
-// sort of the sharded sort after its exchange, glu_dist_impl.hpp).
+// sort of the sharded sort after its exchange, glu_dist.hip).
 //
 // A segmented pass is the stable counting pass of the reference (k_radix_sort_counting_shader + BlellochScan +
 // k_radix_sort_reordering_shader, glu/RadixSort.hpp:11-183) applied to every SEGMENT of the array on its own, all segments
 // in one launch sequence: dst = segment start + (keys of the segment with a smaller digit) + (keys with this digit earlier
 // in the segment) -- RadixSort.hpp:174-177 with the "global offset" taken per segment.
 //
-// The input is cut into SUB-BLOCKS (host: seg_build_image in glu_hip.hip): element ranges that lie inside one piece of one
+// The input is cut into SUB-BLOCKS (host: seg_build_image in seg_plan.hpp): element ranges that lie inside one piece of one
 // segment and inside one workgroup's share of the work.  Sub-blocks are numbered segment-major, in the stable order of the
 // segment's elements, so a segment's sub-blocks are the contiguous index range [seg_list[g], seg_list[g + 1]).
 //   radix_seg_count_kernel   a workgroup per share, sub-block by sub-block: table[i][d] = #keys of sub-block i with digit d   ([sub-block][digit])
@@ -18,7 +18,7 @@
 
 namespace glu_hip
 {
-// A segmented sort that ENDS IN LDS (glu_hip.hip, seg_run_plan): its first pass is the one on the TOP digit of the bits to sort
+// A segmented sort that ENDS IN LDS (glu_sort_segments.hip, seg_run_plan): its first pass is the one on the TOP digit of the bits to sort
 // by; after it the array is a sequence of runs (segment, top digit), whose starts are the first table row of every segment
 // after that pass's scan.  radix_seg_runs_kernel writes them out and notes the longest run in a device word, the GATE: when it
 // fits an LDS tile (gate_cap: the capacity of the largest tile geometry that is enqueued) the pass's scatter and the in-LDS pass

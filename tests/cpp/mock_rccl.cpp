@@ -1,4 +1,4 @@
-// mock_rccl.cpp -- TEST DOUBLE for the nine librccl entry points glu_dist_* binds (gl-radix-sort_amd/csrc/glu_dist_impl.hpp).
+// mock_rccl.cpp -- TEST DOUBLE for the nine librccl entry points glu_dist_* binds (gl-radix-sort_amd/csrc/glu_dist.hip).
 //
 // RCCL refuses two ranks on one GPU, and the GPU box of this project has one GPU: the multi-rank code of the sharded sort
 // (plan with world > 1, send / receive offsets, receive order, empty shards, the lower-byte fallback agreed between

@@ -195,7 +195,7 @@ def test_rccl_test_double_exports_what_the_library_binds(built):
     glu_dist_* looks up with dlsym -- and the product must not mention it."""
     import re
 
-    src = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "glu_dist_impl.hpp")).read()
+    src = open(os.path.join(ROOT, "gl-radix-sort_amd", "csrc", "glu_dist.hip")).read()
     bound = set(re.findall(r'sym\("(nccl\w+)"\)', src))
     assert len(bound) == 9
     mock = os.path.join(ROOT, "tests", "cpp", "bin", "libmock_rccl.so")

@@ -344,3 +344,77 @@ def test_segmented_sort_lds_ending_back_to_back_with_changing_outcomes(G):
         assert (kout.cpu().numpy().view(np.uint32) == ek).all() and (vout.cpu().numpy().view(np.uint32) == ev).all()
     rep = sorter.read_seg_finish()
     assert rep["attempted"] == 1 and rep["accepted"] == 0, rep  # (the last one was a refused one)
+
+
+# ---- the segmented sort and the long runs of a whole-key sort share kernel instantiations (the SEG line scatter, the segmented count
+# and scan: glu_sort_segments.hip), and each launcher opts them into large dynamic LDS the first time IT runs in a process: whichever
+# comes first, both sorts must come out right.  One fresh process per order.
+
+_TWO_LAUNCHERS_CHILD = r"""
+import json, sys
+import numpy as np
+import glu_hip as G
+import oracle as O
+
+rng = np.random.default_rng(17)
+
+
+def segmented():
+    n, nseg = 65536 + 77, 8  # (the smallest count that takes the segmented passes; hipMalloc aligns the arrays)
+    keys = rng.integers(0, 2**32, n, dtype=np.uint32)
+    vals = np.arange(n, dtype=np.uint32)
+    length = rng.multinomial(n, np.ones(24) / 24).astype(np.uint64)
+    begin = np.concatenate([[0], np.cumsum(length)[:-1]]).astype(np.uint64)
+    seg = np.tile(np.arange(nseg, dtype=np.uint32), 3)
+    kin, vin = G.ShaderStorageBuffer(keys), G.ShaderStorageBuffer(vals)
+    kout, vout = G.ShaderStorageBuffer(size=n * 4), G.ShaderStorageBuffer(size=n * 4)
+    G.RadixSort().run_segments_ptr(kin.device_ptr(), vin.device_ptr(), kout.device_ptr(), vout.device_ptr(), n, begin, length, seg, nseg, 24)
+    G.synchronize()
+    ek, ev = [], []
+    for g in range(nseg):
+        at = [i for i in range(24) if seg[i] == g]
+        k = np.concatenate([keys[int(begin[i]):int(begin[i] + length[i])] for i in at])
+        v = np.concatenate([vals[int(begin[i]):int(begin[i] + length[i])] for i in at])
+        k, v = O.stable_sort_pairs(k, v, 24)
+        ek.append(k), ev.append(v)
+    return bool((kout.get_data(np.uint32) == np.concatenate(ek)).all() and (vout.get_data(np.uint32) == np.concatenate(ev)).all())
+
+
+def whole_keys():
+    n = (1 << 22) + 321
+    keys = rng.integers(0, 2**32, n, dtype=np.uint32)
+    keys[rng.choice(n, 9000, replace=False)] &= np.uint32(0x0000FFFF)  # one run of 9000 pairs, longer than the in-LDS pass's tile
+    vals = np.arange(n, dtype=np.uint32)
+    sorter = G.RadixSort(options={"SORT_PAIR_MIN": 1, "SORT_FINISH_MIN": 1})
+    kb, vb = G.ShaderStorageBuffer(keys), G.ShaderStorageBuffer(vals)
+    sorter(kb, vb, n)
+    G.synchronize()
+    ek, ev = O.stable_sort_pairs(keys, vals)
+    return bool((kb.get_data(np.uint32) == ek).all() and (vb.get_data(np.uint32) == ev).all()), sorter.read_finish(), sorter.read_long_runs()
+
+
+report = {}
+for which in sys.argv[1].split(","):
+    if which == "segmented":
+        report["segmented"] = segmented()
+    else:
+        report["whole"], report["finish"], report["long_runs"] = whole_keys()
+print(json.dumps(report))
+"""
+
+
+def test_segmented_sort_and_long_runs_in_either_order_in_a_fresh_process(G):
+    import json
+    import os
+    import subprocess
+    import sys
+
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([p for p in sys.path if p]))
+    for order in ("segmented,whole", "whole,segmented"):
+        p = subprocess.run([sys.executable, "-c", _TWO_LAUNCHERS_CHILD, order], capture_output=True, text=True, env=env, timeout=300)
+        assert p.returncode == 0, (order, p.stdout[-2000:], p.stderr[-4000:])
+        report = json.loads(p.stdout.strip().splitlines()[-1])
+        assert report["segmented"] is True, (order, report)
+        assert report["whole"] is True, (order, report)
+        assert report["finish"]["attempted"] == 1 and report["finish"]["accepted"] == 1, (order, report)
+        assert report["long_runs"]["runs"] >= 1, (order, report)
