@@ -308,6 +308,62 @@ def test_two_objects_on_two_streams_concurrently(G):
             assert (kt.cpu().numpy().view(np.uint32) == ek).all() and (vt.cpu().numpy().view(np.uint32) == ev).all()
 
 
+MALFORMED_TOTAL = 40000
+MALFORMED_GUARD = 512  # elements of poison in front of and behind the arrays; every malformed entry exceeds `total` by less
+MALFORMED_OFFSETS = {
+    # every segment ends below its begin
+    "descending": [MALFORMED_TOTAL, 30000, 20000, 5000, 300, 0],
+    # every segment ends beyond total, or begins there and ends below its begin
+    "beyond_total": [0, MALFORMED_TOTAL + 1, MALFORMED_TOTAL + 300, 5, MALFORMED_TOTAL + 5, 100, MALFORMED_TOTAL + 511],
+    # well-formed segments of every class, pairwise disjoint, in front of and among malformed ones
+    "mixed": [0, 300, 900, 5900, 26000, 30000, MALFORMED_TOTAL + 50, 35000, 36000, MALFORMED_TOTAL + 511, 31000, 31000, 32000,
+              MALFORMED_TOTAL + 1],
+}
+
+
+@pytest.mark.parametrize("key_type", ["uint32", "uint64"])
+@pytest.mark.parametrize("case", ["descending", "beyond_total", "mixed"])
+def test_malformed_offsets_touch_nothing_outside_the_array(G, case, key_type):
+    """A segment whose end is below its begin or beyond `total` is empty to every kernel: the call returns GLU_OK, the poison in front
+    of and behind the keys and the values is intact (a kernel that trusted an end up to 511 elements beyond `total` would sort poison
+    into the array), [0, total) is a permutation of what it held with every value still beside its key, and every well-formed segment
+    that overlaps no malformed one (taken by its span between begin and end, cut at total) is sorted exactly."""
+    import torch
+
+    total, guard, offsets = MALFORMED_TOTAL, MALFORMED_GUARD, MALFORMED_OFFSETS[case]
+    assert max(offsets) < total + guard
+    rng = np.random.default_rng(600 + len(case))
+    u = np.dtype(key_type)
+    keys = rng.integers(0, 2 ** (8 * u.itemsize), total, dtype=u)
+    keys[::3] &= u.type(0xFFFF)  # ties: the values tell a stable sort from another one
+    vals = np.arange(total, dtype=np.uint32)
+    poison_k, poison_v = np.full(guard, 0xA5A5A5A5A5A5A5A5 >> (64 - 8 * u.itemsize), dtype=u), np.full(guard, 0xA5A5A5A5, dtype=np.uint32)
+    kt, vt = to_device(np.concatenate([poison_k, keys, poison_k])), to_device(np.concatenate([poison_v, vals, poison_v]))
+    ot = to_device(np.asarray(offsets, dtype=np.uint32))
+    sorter = G.RadixSort()
+    sorter.sort_batch_offsets_ptr(kt.data_ptr() + guard * u.itemsize, vt.data_ptr() + guard * 4, total, ot.data_ptr(), len(offsets) - 1, key_type,
+                                  torch.cuda.current_stream().cuda_stream)  # (GluError if the status is not GLU_OK)
+    torch.cuda.synchronize()
+    gk, gv = kt.cpu().numpy().view(u), vt.cpu().numpy().view(np.uint32)
+    assert (gk[:guard] == poison_k).all() and (gk[guard + total:] == poison_k).all(), "the call wrote keys outside the array"
+    assert (gv[:guard] == poison_v).all() and (gv[guard + total:] == poison_v).all(), "the call wrote values outside the array"
+    assert (ot.cpu().numpy().view(np.uint32) == np.asarray(offsets, dtype=np.uint32)).all(), "the call wrote to the offsets"
+    gk, gv = gk[guard:guard + total], gv[guard:guard + total]
+    assert (np.sort(gv) == vals).all(), "[0, total) is no permutation of what it held"
+    assert (gk == keys[gv]).all(), "a value left its key"
+    pairs = list(zip(offsets[:-1], offsets[1:]))
+    malformed = [(min(b, e), min(max(b, e), total)) for b, e in pairs if e < b or e > total]
+    clear = [(b, e) for b, e in pairs if b <= e <= total and not any(lo < e and b < hi for lo, hi in malformed)]
+    assert case != "mixed" or {G.plan_batch(e - b, u.itemsize)[0] for b, e in clear} == {1, 2, 3}, "the clear segments miss a class"
+    ek, ev = keys.copy(), vals.copy()
+    for b, e in clear:
+        order = np.argsort(keys[b:e], kind="stable")
+        ek[b:e], ev[b:e] = keys[b:e][order], vals[b:e][order]
+        assert (gk[b:e] == ek[b:e]).all() and (gv[b:e] == ev[b:e]).all(), (case, key_type, b, e)
+    rb = sorter.read_batch()
+    assert rb["wave"] + rb["block"] + rb["long"] <= sum(1 for b, e in pairs if b < e <= total)
+
+
 def test_argument_checks(G):
     import torch
 
