@@ -18,9 +18,10 @@ struct glu_scan_s
     // the batched scan: the list counts and the segment lists of a call; the per-chunk partials of long segments
     glu_hip::host::Scratch batch_lists;
     glu_hip::host::Scratch batch_partials;
+    glu_hip::host::Scratch batch_whole; // the two offset words of the one-segment form, written on the device
     glu_hip::host::LastBatch last_batch; // segments per class of the last batched call (glu_scan_read_batch)
     void release()
     {
-        for (glu_hip::host::Scratch* s : {&sums, &chain, &ticket, &batch_lists, &batch_partials}) s->release();
+        for (glu_hip::host::Scratch* s : {&sums, &chain, &ticket, &batch_lists, &batch_partials, &batch_whole}) s->release();
     }
 };

@@ -18,7 +18,8 @@ __global__ __launch_bounds__(kSbThreads) void key_runs_scan_kernel(uint32_t* __r
     if (threadIdx.x == 0) last = tiles ? tile_counts[tiles - 1] : 0u;
     __syncthreads();
     uint32_t phase = 0;
-    scan_batch_range<uint32_t, 1>(reinterpret_cast<T*>(tile_counts), tiles, zero_elem<uint32_t, 1>(), threadIdx.x, wsum, phase);
+    scan_batch_range<OP_SUM, false, uint32_t, 1, false, true>(nullptr, reinterpret_cast<T*>(tile_counts), tiles, zero_elem<uint32_t, 1>(), threadIdx.x,
+                                                              wsum, phase);
     __syncthreads(); // (the last count's scan was stored by another thread of this workgroup)
     if (threadIdx.x == 0)
     {

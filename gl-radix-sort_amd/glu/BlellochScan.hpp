@@ -11,6 +11,8 @@ namespace glu
     /// Exclusive prefix sum (`+`, identity 0), in place, over `num_partitions` adjacent partitions of `count`
     /// elements each.  Keeps the reference's name although the device algorithm is a chunked
     /// reduce-then-scan rather than Blelloch's up/down sweep; results are identical for integer types.
+    /// The batched forms below scan segments given by device offsets, and with an operator and a kind also inclusively, with
+    /// Reduce's other operators, and into a second array.
     class BlellochScan
     {
     public:
@@ -51,6 +53,26 @@ namespace glu
         {
             GLU_CHECK_STATUS(glu_scan_run_batch_offsets_ptr(m_impl, device_data, total, device_offsets, num_segments, stream));
         }
+        /// The batched scan with any of Reduce's operators, exclusive or inclusive (glu_scan_run_batch_offsets_op_ptr in
+        /// glu_hip.h): device_out receives the scan of every segment of device_data at the same positions and is not touched
+        /// outside the segments; nullptr or device_data itself: in place.  Otherwise device_data is only read, and the two arrays
+        /// of `total` elements must not overlap.  The identities of an exclusive scan are Reduce's: 0, 1, the type's largest
+        /// value (+infinity) for Min, its lowest (-infinity) for Max.
+        void scan_batch_offsets(const void* device_data, void* device_out, size_t total, const uint32_t* device_offsets, size_t num_segments,
+                                glu_reduce_operator op, glu_scan_kind kind, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_scan_run_batch_offsets_op_ptr(m_impl, device_data, device_out, total, device_offsets, num_segments, op, kind, stream));
+        }
+        /// The scan of a whole array of `total` (< 2^32) elements as one segment, no offsets array needed: cumsum, cumprod,
+        /// cummin and cummax.  Capturable after prepare_batch(total, 1).
+        void inclusive_scan(const void* device_data, void* device_out, size_t total, glu_reduce_operator op, void* stream = nullptr)
+        {
+            scan_batch_offsets(device_data, device_out, total, nullptr, 1, op, GLU_SCAN_INCLUSIVE, stream);
+        }
+        void exclusive_scan(const void* device_data, void* device_out, size_t total, glu_reduce_operator op, void* stream = nullptr)
+        {
+            scan_batch_offsets(device_data, device_out, total, nullptr, 1, op, GLU_SCAN_EXCLUSIVE, stream);
+        }
         /// Scan by key (KeyRuns.hpp): the runs of `k.keys` taken by `runs`, then the values of every run replaced by their own
         /// exclusive scan, in place -- the two calls, on the caller's stream, with nothing between them.  device_values: k.count
         /// elements of the data type.
@@ -59,6 +81,15 @@ namespace glu
             GLU_CHECK_ARGUMENT(k.max_runs <= ((size_t) 1 << 24), "scan_by_key: max_runs %zu exceeds 2^24", k.max_runs);
             runs(k.keys, k.count, k.key_bits, k.begin_bit, k.end_bit, k.unique_keys, k.offsets, k.max_runs, k.num_runs, stream);
             scan_batch_offsets(device_values, k.count, k.offsets, k.max_runs, stream);
+        }
+        /// Scan by key with an operator and a kind: a running maximum, minimum, sum or product per run of keys, stored to
+        /// device_out (nullptr: in place, over device_values).
+        void scan_by_key(KeyRuns& runs, const KeyRunsArrays& k, const void* device_values, glu_reduce_operator op, glu_scan_kind kind,
+                         void* device_out = nullptr, void* stream = nullptr)
+        {
+            GLU_CHECK_ARGUMENT(k.max_runs <= ((size_t) 1 << 24), "scan_by_key: max_runs %zu exceeds 2^24", k.max_runs);
+            runs(k.keys, k.count, k.key_bits, k.begin_bit, k.end_bit, k.unique_keys, k.offsets, k.max_runs, k.num_runs, stream);
+            scan_batch_offsets(device_values, device_out, k.count, k.offsets, k.max_runs, op, kind, stream);
         }
         /// Scratch for batched scans of up to `total` elements in up to `num_segments` segments (they then allocate nothing and
         /// can be captured into a graph).

@@ -96,6 +96,7 @@ SYMBOLS = [
     ("glu_scan_run", _int, [_vp, _u32, _sz, _sz]),
     ("glu_scan_run_ptr", _int, [_vp, _vp, _sz, _sz, _vp]),
     ("glu_scan_run_batch_offsets_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    ("glu_scan_run_batch_offsets_op_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _sz, _int, _int, _vp]),
     ("glu_scan_prepare_batch", _int, [_vp, _sz, _sz]),
     ("glu_scan_plan_batch", _int, [_sz, _u32, _P(_u32), _P(_u32)]),
     ("glu_scan_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
@@ -1020,18 +1021,33 @@ class BlellochScan(_Handle):
     def run_ptr(self, data_ptr, count, num_partitions=1, stream=None):
         check(lib().glu_scan_run_ptr(self._h, _vp(data_ptr), count, num_partitions, _vp(stream)))
 
-    def run_batch_offsets_ptr(self, data_ptr, total, offsets_ptr, num_segments, stream=None):
+    OPS = {"sum": 0, "mul": 1, "min": 2, "max": 3}  # glu_reduce_operator
+
+    def run_batch_offsets_ptr(self, data_ptr, total, offsets_ptr, num_segments, stream=None, out_ptr=None, op="sum", inclusive=False):
         """Elements [offsets[s], offsets[s+1]) become their own exclusive scan, in place, for every segment (offsets: num_segments
-        + 1 uint32 on the DEVICE) (glu_scan_run_batch_offsets_ptr)."""
-        check(lib().glu_scan_run_batch_offsets_ptr(self._h, _vp(data_ptr), total, _vp(offsets_ptr), num_segments, _vp(stream)))
+        + 1 uint32 on the DEVICE) (glu_scan_run_batch_offsets_ptr).  With `out_ptr`, an `op` ("sum", "mul", "min", "max" or a
+        glu_reduce_operator) or `inclusive`: that scan, stored to `out_ptr` where one is given, `data_ptr` then only read
+        (glu_scan_run_batch_offsets_op_ptr)."""
+        if out_ptr is None and op in ("sum", 0) and not inclusive:
+            check(lib().glu_scan_run_batch_offsets_ptr(self._h, _vp(data_ptr), total, _vp(offsets_ptr), num_segments, _vp(stream)))
+            return
+        check(lib().glu_scan_run_batch_offsets_op_ptr(self._h, _vp(data_ptr), _vp(out_ptr), total, _vp(offsets_ptr), num_segments,
+                                                      self.OPS.get(op, op), int(bool(inclusive)), _vp(stream)))
+
+    def run_whole_ptr(self, data_ptr, total, stream=None, out_ptr=None, op="sum", inclusive=False):
+        """The scan of the whole array [0, total) as one segment, no offsets array needed: cumsum, cumprod, cummin, cummax
+        (glu_scan_run_batch_offsets_op_ptr with offsets == NULL)."""
+        check(lib().glu_scan_run_batch_offsets_op_ptr(self._h, _vp(data_ptr), _vp(out_ptr), total, None, 1, self.OPS.get(op, op),
+                                                      int(bool(inclusive)), _vp(stream)))
 
     def run_by_key_ptr(self, runs, keys_ptr, values_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr=None,
-                       key_bits=32, begin_bit=0, end_bit=None, stream=None):
+                       key_bits=32, begin_bit=0, end_bit=None, stream=None, out_ptr=None, op="sum", inclusive=False):
         """Scan by key: runs.run_ptr on the keys, then the values of every run become their own exclusive scan, in place -- the
-        two calls on one stream (glu::BlellochScan::scan_by_key).  max_runs <= 2^24."""
+        two calls on one stream (glu::BlellochScan::scan_by_key).  max_runs <= 2^24.  out_ptr, op, inclusive: as in
+        run_batch_offsets_ptr."""
         _check_composed_runs(max_runs)
         runs.run_ptr(keys_ptr, count, offsets_ptr, max_runs, num_runs_ptr, unique_keys_ptr, key_bits, begin_bit, end_bit, stream)
-        self.run_batch_offsets_ptr(values_ptr, count, offsets_ptr, max_runs, stream)
+        self.run_batch_offsets_ptr(values_ptr, count, offsets_ptr, max_runs, stream, out_ptr=out_ptr, op=op, inclusive=inclusive)
 
     def prepare_batch(self, total, num_segments):
         """Grow-only scratch for batched scans of up to `total` elements in up to `num_segments` segments: after it the call

@@ -435,9 +435,44 @@ GLU_API glu_status glu_scan_run_ptr(glu_scan scan, void* data, size_t count, siz
  * offsets: DEVICE array of num_segments + 1 uint32, non-decreasing, in elements of the object's data type */
 GLU_API glu_status glu_scan_run_batch_offsets_ptr(glu_scan scan, void* data, size_t total, const uint32_t* offsets,
                                                   size_t num_segments, void* stream);
+
+/* The batched scan with any of Reduce's four operators, exclusive or inclusive, in place or into a second array: cumsum, cumprod,
+ * cummin and cummax per segment.  The object is the one glu_scan_create makes; its scratch does not depend on the operator, so
+ * `op` and `kind` are arguments of the call and may change from call to call.  For every segment [b, e) = [offsets[s],
+ * offsets[s+1]) and every i in it, with x the ORIGINAL contents of `data`:
+ *   - GLU_SCAN_EXCLUSIVE: out[i] = x[b] OP ... OP x[i-1], and out[b] = the identity of OP: 0 for Sum, 1 for Mul, +infinity (floats)
+ *     or the type's maximum (integers) for Min, -infinity or the type's lowest value for Max (the values the batched reduce gives
+ *     an empty segment).
+ *   - GLU_SCAN_INCLUSIVE: out[i] = exclusive[i] OP x[i].  Under Sum a first element -0.0 therefore comes out as +0.0 (0 + -0.0).
+ *   - Vector types are scanned per component.  Integers wrap modulo 2^32 as they do in Reduce.  The earlier operand is always on
+ *     the left.  Float Min / Max are `a < b ? a : b` and `a > b ? a : b` (Reduce's), which do not commute on NaN: results at and
+ *     behind a NaN in a segment are unspecified, and which of two zeros of different sign comes out is, too.
+ *   - out == NULL or out == data: in place.  Otherwise `data` is only read and `out` receives the results at the same positions;
+ *     positions of `out` outside the segments are not touched.  `out` is aligned like `data` (to the element size, 16 bytes at
+ *     most) and need not share data's address modulo 16: which element goes to which lane follows data's address alone, 16-byte
+ *     stores are used only where they are aligned on out's side, and the results are the same bits wherever `out` lies.  Ranges
+ *     of `total` elements that overlap without being identical: GLU_ERROR_INVALID_ARGUMENT.
+ *   - offsets == NULL with num_segments == 1: the one segment [0, total), the scan of a whole array.  The two offset words are
+ *     written into a scratch of the object by a small kernel that takes `total` as an argument: no host-to-device copy, the call
+ *     stays capturable (glu_scan_prepare_batch reserves that scratch too).  total < 2^32 here as well.  NULL offsets with more
+ *     than one segment: GLU_ERROR_INVALID_ARGUMENT.
+ *   - An `op` outside glu_reduce_operator or a `kind` outside glu_scan_kind: GLU_ERROR_INVALID_ARGUMENT.
+ *   - Everything else is the contract of glu_scan_run_batch_offsets_ptr above: the limits, device offsets the host never reads,
+ *     malformed segments empty to every kernel, enqueue only, the same classes (glu_scan_plan_batch, glu_scan_read_batch), no
+ *     atomics on values, no look-back, the same bits every time; a segment's result depends on its data, its length, data's
+ *     address modulo 16 and its class only.  The chunk partials of the long class are combined with `op` and scanned exclusively
+ *     whatever `kind` is.  op = GLU_REDUCE_SUM, kind = GLU_SCAN_EXCLUSIVE, in place is glu_scan_run_batch_offsets_ptr itself. */
+typedef enum glu_scan_kind
+{
+    GLU_SCAN_EXCLUSIVE = 0,
+    GLU_SCAN_INCLUSIVE = 1
+} glu_scan_kind;
+GLU_API glu_status glu_scan_run_batch_offsets_op_ptr(glu_scan scan, const void* data, void* out, size_t total,
+                                                     const uint32_t* offsets, size_t num_segments, glu_reduce_operator op,
+                                                     glu_scan_kind kind, void* stream);
 /* Grow-only scratch so that the call above allocates nothing (and can be captured) for batches of up to `total` (< 2^32) elements
  * in up to `num_segments` (<= 2^24) segments: the segment lists (4 bytes per segment and class that fits `total`, 16 bytes per
- * 32 KiB chunk) and one partial sum per chunk of the long class. */
+ * 32 KiB chunk), one partial per chunk of the long class, and the two offset words of the one-segment form. */
 GLU_API glu_status glu_scan_prepare_batch(glu_scan scan, size_t total, size_t num_segments);
 /* Host only, no device (unit-testable, like glu_reduce_plan_batch): the class of a segment of `count` elements of `elem_bytes`
  * (4, 8, 16 or 32) bytes: path 0 = nothing to do, 1 = a wave (or part of a wave) per segment, 2 = a workgroup per segment,
