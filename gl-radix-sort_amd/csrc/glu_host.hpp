@@ -18,7 +18,8 @@
 //   glu_scan_batch.hip        the batched scan: every segment of an array scanned on its own (scan_batch_kernels.hpp)
 //   glu_key_runs.hip          key runs: the offsets of the runs of equal keys, for the three batched units (key_runs_kernels.hpp)
 //   glu_select.hip            select: stable stream compaction by a stencil and a comparison (select_kernels.hpp)
-//   glu_sorted_search.hip     sorted search: lower and upper bounds of many needles in a sorted haystack (sorted_search_kernels.hpp)
+//   glu_sorted_search.hip     sorted search: lower and upper bounds of many needles in a sorted haystack (sorted_search_kernels.hpp),
+//                             and every segment's needles in its own haystack (sorted_search_batch_kernels.hpp over search_batch_walk.hpp)
 //   glu_merge.hip             merge: two sorted arrays of keys and values into one, stable (merge_kernels.hpp over merge_path.hpp)
 //   glu_histogram.hip         histogram: counts per bin over even bins or sorted edges (histogram_kernels.hpp over histogram_bins.hpp)
 //   glu_expand.hip            expand: segment, rank and item per element from the offsets (expand_kernels.hpp over expand_path.hpp)

@@ -1,6 +1,8 @@
 // glu_sorted_search.hip -- sorted search of libglu_hip.so (sorted_search_kernels.hpp): glu_sorted_search_create,
 // glu_sorted_search_destroy, glu_sorted_search_prepare, glu_sorted_search_set_option, glu_sorted_search_index_ptr,
-// glu_sorted_search_run_ptr, glu_sorted_search_plan, glu_sorted_search_last.
+// glu_sorted_search_run_ptr, glu_sorted_search_plan, glu_sorted_search_last, and the batched search
+// (sorted_search_batch_kernels.hpp over search_batch_walk.hpp): glu_sorted_search_run_batch_ptr,
+// glu_sorted_search_run_batch_offsets_ptr, glu_sorted_search_set_batch_window, glu_sorted_search_plan_batch.
 // The library's other translation units: glu_host.hpp.
 #include <hip/hip_runtime.h>
 
@@ -8,12 +10,14 @@
 #include <cstring>
 
 #include "glu_sorted_search_object.hpp"
+#include "sorted_search_batch_kernels.hpp"
 #include "sorted_search_kernels.hpp"
 
 using namespace glu_hip;
 using namespace glu_hip::host;
 
 static_assert(kSearchLevelsMax == kSearchMaxLevels, "the host's level rule fills the kernels' level table");
+static_assert(kSearchBatchWindowUnset == GLU_SEARCH_BATCH_WINDOW_DEFAULT, "the header's default window is the walk's unset window");
 
 namespace
 {
@@ -135,9 +139,170 @@ glu_status check_hay(glu_sorted_search_s* s, const void* hay, size_t hay_count, 
     GLU_TRY(check_aligned(hay, key_bytes_of(key_type), "hay", "the key size"));
     return check_top_entries(s->top_entries, key_bytes_of(key_type));
 }
+
+// ---- the batched search ------------------------------------------------------------------------------------------------------------
+glu_status check_batch_window(uint64_t keys, uint32_t key_bytes)
+{
+    if (keys == kSearchBatchWindowUnset || search_batch_window_ok(keys, key_bytes)) return GLU_OK;
+    return fail(GLU_ERROR_INVALID_ARGUMENT, "the batch window must be 0 or lie in [%u, %u] for %u-byte keys (got %llu)", kSearchBatchMinWindow,
+                search_batch_max_window(key_bytes), key_bytes, (unsigned long long) keys);
+}
+
+// both forms behind their size checks.  hay_offsets NULL: equal partitions of hay_count keys; needle_offsets NULL: equal rows of
+// needle_row needles.
+struct BatchCall
+{
+    glu_sorted_search_s* s;
+    const void* hay;
+    size_t hay_total, hay_count;
+    const uint32_t* hay_offsets;
+    const void* needles;
+    size_t needle_total, needle_row;
+    const uint32_t* needle_offsets;
+    size_t num_segments;
+    int key_type;
+    uint32_t* out_lower;
+    uint32_t* out_upper;
+    void* stream;
+};
+
+template<typename K, int BOUNDS>
+void launch_batch(const SearchBatchArgs<K>& a, uint32_t grid, hipStream_t stream)
+{
+    if (a.needle_offsets)
+        hipLaunchKernelGGL((sorted_search_batch_kernel<K, BOUNDS, true>), dim3(grid), dim3(kTileThreads), 0, stream, a);
+    else
+        hipLaunchKernelGGL((sorted_search_batch_kernel<K, BOUNDS, false>), dim3(grid), dim3(kTileThreads), 0, stream, a);
+}
+
+template<typename K>
+glu_status launch_batch(const BatchCall& c, uint32_t window)
+{
+    SearchBatchArgs<K> a = {};
+    a.hay = (const K*) c.hay;
+    a.hay_offsets = c.hay_offsets;
+    a.needle_offsets = c.needle_offsets;
+    a.out_lower = c.out_lower;
+    a.out_upper = c.out_upper;
+    a.needles = tile_span<K, kSearchBatchPacks>(c.needles, c.needle_total);
+    a.rows = search_batch_make_rows((uint32_t) c.needle_row, (uint32_t) c.hay_count);
+    a.hay_total = (uint32_t) c.hay_total;
+    a.num_segments = (uint32_t) c.num_segments;
+    a.window = window;
+    a.xf = key_xf_of(c.key_type);
+    const uint32_t grid = tile_grid(a.needles.tiles);
+    const hipStream_t st = pick_stream(c.stream);
+    if (c.out_lower && c.out_upper)
+        launch_batch<K, SEARCH_BOTH>(a, grid, st);
+    else if (c.out_lower)
+        launch_batch<K, SEARCH_LOWER>(a, grid, st);
+    else
+        launch_batch<K, SEARCH_UPPER>(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    return GLU_OK;
+}
+
+glu_status run_batch(const BatchCall& c)
+{
+    const uint32_t kb = key_bytes_of(c.key_type);
+    c.s->last = {(uint32_t) GLU_SEARCH_PATH_BATCH, 0u, 0u};
+    if (!c.num_segments || !c.needle_total) return GLU_OK; // nothing to find: no array is looked at
+    if (c.hay_total && !c.hay) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid hay buffer");
+    if (!c.needles) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid needles buffer");
+    if (!c.out_lower && !c.out_upper) return fail(GLU_ERROR_INVALID_ARGUMENT, "out_lower and out_upper are both NULL");
+    GLU_TRY(check_aligned(c.hay, kb, "hay", "the key size"));
+    GLU_TRY(check_aligned(c.needles, kb, "needles", "the key size"));
+    GLU_TRY(check_aligned_4(c.out_lower, "out_lower"));
+    GLU_TRY(check_aligned_4(c.out_upper, "out_upper"));
+    GLU_TRY(check_aligned_4(c.hay_offsets, "hay_offsets"));
+    GLU_TRY(check_aligned_4(c.needle_offsets, "needle_offsets"));
+    const size_t out_bytes = c.needle_total * sizeof(uint32_t), offsets_bytes = (c.num_segments + 1) * sizeof(uint32_t);
+    GLU_TRY(check_disjoint({{c.out_lower, out_bytes, "out_lower"}, {c.out_upper, out_bytes, "out_upper"}},
+                           {{c.hay, c.hay_total * kb, "hay"},
+                            {c.needles, c.needle_total * kb, "needles"},
+                            {c.hay_offsets, offsets_bytes, "hay_offsets"},
+                            {c.needle_offsets, offsets_bytes, "needle_offsets"}},
+                           kOutputsAfterInputs));
+    GLU_TRY(check_batch_window(c.s->batch_window, kb));
+    const uint32_t window = search_batch_plan(c.needle_total, kb, c.s->batch_window).window;
+    GLU_TRY(kb == 8 ? launch_batch<uint64_t>(c, window) : launch_batch<uint32_t>(c, window));
+    c.s->last.kernels = 1;
+    return GLU_OK;
+}
 } // namespace
 
 extern "C" {
+
+glu_status glu_sorted_search_plan_batch(size_t needle_total, glu_key_type key_type, uint32_t window_keys, uint32_t* tile, uint32_t* tiles,
+                                        uint32_t* window_keys_used, uint32_t* kernels)
+{
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_below_2_32(needle_total, "needle_total"));
+    const uint32_t kb = key_bytes_of((int) key_type);
+    GLU_TRY(check_batch_window(window_keys, kb));
+    const SearchBatchPlan p = search_batch_plan(needle_total, kb, window_keys);
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(window_keys_used, p.window);
+    store(kernels, p.kernels);
+    return GLU_OK;
+}
+
+glu_status glu_sorted_search_set_batch_window(glu_sorted_search search, uint32_t keys)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(search, "search"));
+    // the widest range here (4-byte keys end at 8192); a call holds it against its own key width
+    if (keys != GLU_SEARCH_BATCH_WINDOW_DEFAULT && !search_batch_window_ok(keys, 4))
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "the batch window must be 0 or lie in [%u, %u] (got %u)", kSearchBatchMinWindow,
+                    search_batch_max_window(4), keys);
+    search->batch_window = keys;
+    return GLU_OK;
+}
+
+glu_status glu_sorted_search_run_batch_ptr(glu_sorted_search search, const void* hay, size_t hay_count, const void* needles, size_t needle_count,
+                                           size_t num_partitions, glu_key_type key_type, uint32_t* out_lower, uint32_t* out_upper, void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(search, "search"));
+    GLU_TRY(check_key_type((int) key_type));
+    const size_t most = ((size_t) 1 << 32) - 1;
+    if (num_partitions > most || (hay_count && num_partitions > most / hay_count))
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "hay_count * num_partitions must stay below 2^32 (got hay_count %zu, num_partitions %zu)", hay_count,
+                    num_partitions);
+    if (needle_count && num_partitions > most / needle_count)
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "needle_count * num_partitions must stay below 2^32 (got needle_count %zu, num_partitions %zu)",
+                    needle_count, num_partitions);
+    return run_batch({search, hay, hay_count * num_partitions, hay_count, nullptr, needles, needle_count * num_partitions, needle_count, nullptr,
+                      num_partitions, (int) key_type, out_lower, out_upper, stream});
+}
+
+glu_status glu_sorted_search_run_batch_offsets_ptr(glu_sorted_search search, const void* hay, size_t hay_total, const uint32_t* hay_offsets,
+                                                   const void* needles, size_t needle_total, const uint32_t* needle_offsets, size_t num_segments,
+                                                   glu_key_type key_type, uint32_t* out_lower, uint32_t* out_upper, void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(search, "search"));
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_batch_segments(num_segments));
+    GLU_TRY(check_batch_total(hay_total));
+    GLU_TRY(check_batch_total(needle_total));
+    size_t needle_row = 0;
+    if (num_segments && needle_total)
+    {
+        GLU_TRY(check_not_null(hay_offsets, "hay_offsets"));
+        if (!needle_offsets)
+        {
+            if (needle_total % num_segments)
+                return fail(GLU_ERROR_INVALID_ARGUMENT,
+                            "needle_total must be a multiple of num_segments where needle_offsets is NULL (got needle_total %zu, num_segments %zu)",
+                            needle_total, num_segments);
+            needle_row = needle_total / num_segments;
+        }
+    }
+    return run_batch({search, hay, hay_total, 0, hay_offsets, needles, needle_total, needle_row, needle_offsets, num_segments, (int) key_type,
+                      out_lower, out_upper, stream});
+}
 
 glu_status glu_sorted_search_plan(size_t hay_count, size_t needle_count, glu_key_type key_type, uint32_t top_entries, uint32_t* path,
                                   uint32_t* levels, uint32_t* fanout, size_t* index_bytes)

@@ -3,12 +3,14 @@
 #pragma once
 
 #include "glu_tile_host.hpp"
+#include "search_batch_walk.hpp"
 
 struct glu_sorted_search_s
 {
     glu_hip::host::Scratch index; // the levels 1 .. L of the index, each from a 128-byte boundary
     int path = GLU_SEARCH_PATH_AUTO;
     uint32_t top_entries = 0; // 0: the LDS maximum of the key width
+    uint32_t batch_window = glu_hip::kSearchBatchWindowUnset; // keys staged in LDS by the batched calls; unset: the maximum of the key width
     // the haystack the index in `index` was built from
     struct Built
     {

@@ -22,6 +22,8 @@ SelectStencil_Float, SelectStencil_Double, SelectStencil_Int, SelectStencil_Uint
 SelectOperator_EQ, SelectOperator_NE, SelectOperator_LT, SelectOperator_LE, SelectOperator_GT, SelectOperator_GE = range(6)
 # glu_sorted_search_set_option("PATH", ...) and what glu_sorted_search_plan / glu_sorted_search_last report
 SearchPath_Auto, SearchPath_Direct, SearchPath_Indexed = range(3)
+SearchPath_Batch = 3  # what glu_sorted_search_last reports after a batched call (never an option)
+SEARCH_BATCH_WINDOW_DEFAULT = 0xFFFFFFFF  # set_batch_window / plan_sorted_search_batch: the maximum of the call's key width
 # glu_top_k_set_option("PATH", ...) and what glu_top_k_read_last reports
 TopKPath_Auto, TopKPath_Candidates, TopKPath_Full = range(3)
 KEY_TYPES = {"uint32": 0, "int32": 1, "float32": 2, "uint64": 3, "int64": 4, "float64": 5}  # glu_key_type by numpy dtype name
@@ -127,6 +129,10 @@ SYMBOLS = [
     ("glu_sorted_search_run_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _int, _vp]),
     ("glu_sorted_search_plan", _int, [_sz, _sz, _int, _u32, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_sorted_search_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_sorted_search_run_batch_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _vp, _vp]),
+    ("glu_sorted_search_run_batch_offsets_ptr", _int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _vp]),
+    ("glu_sorted_search_set_batch_window", _int, [_vp, _u32]),
+    ("glu_sorted_search_plan_batch", _int, [_sz, _int, _u32, _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_merge_create", _int, [_P(_vp)]),
     ("glu_merge_destroy", _int, [_vp]),
     ("glu_merge_prepare", _int, [_vp, _sz, _int]),
@@ -383,6 +389,16 @@ def plan_sorted_search(hay_count, needle_count, key_type="uint32", top_entries=0
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_sorted_search_plan(hay_count, needle_count, KEY_TYPES[key_type], top_entries, ctypes.byref(a), ctypes.byref(b),
                                        ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def plan_sorted_search_batch(needle_total, key_type="uint32", window_keys=SEARCH_BATCH_WINDOW_DEFAULT):
+    """(tile, tiles, window_keys_used, kernels) of a batched sorted search of `needle_total` needles (glu_sorted_search_plan_batch;
+    host only): needles per tile, tiles of needles that start on a 16-byte boundary, the window in keys (window_keys: 0, a value in
+    the range of the key width or the default, its maximum), 1 kernel (0 for no needles)."""
+    a, b, c, d = _u32(), _u32(), _u32(), _u32()
+    check(lib().glu_sorted_search_plan_batch(needle_total, KEY_TYPES[key_type], window_keys, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                             ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
 
 
@@ -756,8 +772,30 @@ class SortedSearch(_Handle):
         check(lib().glu_sorted_search_run_ptr(self._h, _vp(hay_ptr), hay_count, _vp(needles_ptr), needle_count, KEY_TYPES[key_type],
                                               _vp(out_lower_ptr), _vp(out_upper_ptr), 1 if reuse_index else 0, _vp(stream)))
 
+    def run_batch_ptr(self, hay_ptr, hay_count, needles_ptr, needle_count, num_partitions, out_lower_ptr=None, out_upper_ptr=None,
+                      key_type="uint32", stream=None):
+        """Row p of `needle_count` needles searched in row p of `hay_count` keys, for num_partitions rows in one kernel; the
+        positions are local to the row, as torch.searchsorted gives them (glu_sorted_search_run_batch_ptr)."""
+        check(lib().glu_sorted_search_run_batch_ptr(self._h, _vp(hay_ptr), hay_count, _vp(needles_ptr), needle_count, num_partitions,
+                                                    KEY_TYPES[key_type], _vp(out_lower_ptr), _vp(out_upper_ptr), _vp(stream)))
+
+    def run_batch_offsets_ptr(self, hay_ptr, hay_total, hay_offsets_ptr, needles_ptr, needle_total, needle_offsets_ptr, num_segments,
+                              out_lower_ptr=None, out_upper_ptr=None, key_type="uint32", stream=None):
+        """The needles of segment s searched in the haystack of segment s, both from device offsets of num_segments + 1 uint32
+        (needle_offsets_ptr None: equal rows of needle_total / num_segments needles); positions local to the segment
+        (glu_sorted_search_run_batch_offsets_ptr)."""
+        check(lib().glu_sorted_search_run_batch_offsets_ptr(self._h, _vp(hay_ptr), hay_total, _vp(hay_offsets_ptr), _vp(needles_ptr),
+                                                            needle_total, _vp(needle_offsets_ptr), num_segments, KEY_TYPES[key_type],
+                                                            _vp(out_lower_ptr), _vp(out_upper_ptr), _vp(stream)))
+
+    def set_batch_window(self, keys):
+        """The most keys of a tile's haystacks that the batched calls stage in LDS: 0 (never), 16 .. 32768 / key bytes, or
+        SEARCH_BATCH_WINDOW_DEFAULT (glu_sorted_search_set_batch_window)."""
+        check(lib().glu_sorted_search_set_batch_window(self._h, keys))
+
     def last(self):
-        """(path, levels, kernels) of what the last index_ptr or run_ptr enqueued (glu_sorted_search_last; no device read)."""
+        """(path, levels, kernels) of what the last index_ptr, run_ptr or batched call enqueued (glu_sorted_search_last; no device
+        read)."""
         a, b, c = _u32(), _u32(), _u32()
         check(lib().glu_sorted_search_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value

@@ -709,14 +709,16 @@ GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* til
  *     allocation inside the call: not capturable; scratch that grows forgets the remembered index).  The kernels and their grids
  *     follow from the counts and the addresses, so a captured call replays on any contents.
  *   - OUT OF SCOPE: a haystack length that lives on the device (the idiom for the unique keys of key runs: pre-fill
- *     unique_keys[0 .. max_runs) with the type's largest key and search all max_runs entries); a segmented search; a special
- *     path for sorted needles (neighbouring lanes already share their lines). */
+ *     unique_keys[0 .. max_runs) with the type's largest key and search all max_runs entries); a special
+ *     path for sorted needles (neighbouring lanes already share their lines).  A search per segment, every segment's needles in
+ *     its own haystack, is glu_sorted_search_run_batch_ptr / glu_sorted_search_run_batch_offsets_ptr below. */
 typedef struct glu_sorted_search_s* glu_sorted_search;
 enum
 {
     GLU_SEARCH_PATH_AUTO = 0,
     GLU_SEARCH_PATH_DIRECT = 1,
-    GLU_SEARCH_PATH_INDEXED = 2
+    GLU_SEARCH_PATH_INDEXED = 2,
+    GLU_SEARCH_PATH_BATCH = 3 /* reported by glu_sorted_search_last after a batched call; not a value of the PATH option */
 };
 GLU_API glu_status glu_sorted_search_create(glu_sorted_search* out);
 GLU_API glu_status glu_sorted_search_destroy(glu_sorted_search search);
@@ -738,6 +740,70 @@ GLU_API glu_status glu_sorted_search_plan(size_t hay_count, size_t needle_count,
 /* What the host enqueued in the object's last index_ptr or run_ptr (no device read): the path taken, the levels of the index
  * used (0 on the DIRECT path), the number of kernels. */
 GLU_API glu_status glu_sorted_search_last(glu_sorted_search search, uint32_t* path, uint32_t* levels, uint32_t* kernels);
+
+/* ---- batched sorted search (not in the reference): every segment's needles in that segment's own haystack, one kernel for the
+ * whole batch, on the same glu_sorted_search object.  torch.searchsorted with a batched sorted sequence (sorted[B, N],
+ * values[B, M]); the upper bound of M uniform numbers per row in that row's CDF (inverse-CDF sampling over the batched scan); the
+ * positions of one side's keys within the matching group of the other after sort -> key runs on both sides, and the rank of a
+ * value within its group.  enc, the six key types and the order are those of glu_sorted_search_run_ptr: the sort's total order on
+ * bits, not select's IEEE comparison.
+ *   - EQUAL PARTITIONS (glu_sorted_search_run_batch_ptr; the shape of glu_reduce_run_batch_ptr): row p of the haystack is
+ *     hay[p * hay_count .. (p + 1) * hay_count), its needles are needles[p * needle_count .. (p + 1) * needle_count).
+ *     hay_count * num_partitions < 2^32 and needle_count * num_partitions < 2^32.
+ *   - DEVICE OFFSETS (glu_sorted_search_run_batch_offsets_ptr): hay_offsets and needle_offsets are device arrays of
+ *     num_segments + 1 uint32, non-decreasing, as key runs writes them; the host never reads them.  Segment s has the haystack
+ *     [hay_offsets[s], hay_offsets[s + 1]) and the needles [needle_offsets[s], needle_offsets[s + 1]).  num_segments <= 2^24,
+ *     hay_total < 2^32, needle_total < 2^32.  needle_offsets == NULL: equal needle rows of needle_total / num_segments (it must
+ *     divide, else GLU_ERROR_INVALID_ARGUMENT): ragged CDFs with M samples each.
+ *   - For segment s with haystack [hb, he) and needles [nb, ne), and every j in [nb, ne):
+ *       out_lower[j] = the number of i in [hb, he) with enc(hay[i]) <  enc(needles[j])
+ *       out_upper[j] = the number of i in [hb, he) with enc(hay[i]) <= enc(needles[j])
+ *     The positions are LOCAL to the segment, in [0, he - hb]: what torch.searchsorted gives per row, what batched top-k writes
+ *     and what the batched gather takes; a caller who wants global positions adds hay_offsets[s] (glu_expand_run_ptr hands it to
+ *     every needle).  Either output may be NULL, not both.  Every entry of a covered needle is written; needles in front of
+ *     needle_offsets[0] or at or behind needle_offsets[num_segments] are not touched (expand's rule).  A segment whose haystack is
+ *     empty gives 0 for all its needles.
+ *   - num_partitions == 0, num_segments == 0 or no needles: nothing is enqueued, GLU_OK, NULL arrays accepted.
+ *   - MALFORMED OFFSETS (decreasing, beyond the total): a segment that ends below its begin or beyond the total is empty, on
+ *     either side.  The result is unspecified positions or untouched entries; no access outside the five arrays happens.  A
+ *     haystack that is not sorted gives unspecified positions in [0, he - hb].
+ *   - GLU_ERROR_INVALID_ARGUMENT, each with a message that names the argument: NULL search; NULL hay or needles with a non-zero
+ *     size; NULL hay_offsets; both outputs NULL; misalignment (hay and needles to the key size, the outputs and the offsets to 4
+ *     bytes); a bad key type; the limits above; an output overlapping hay, needles, either offsets array or the other output; a
+ *     window outside the range of the call's key width.  A refused call writes nothing.
+ *   - ONE KERNEL per call, none where there are no needles.  It is load-balanced over the needles: a workgroup takes tiles of 2048
+ *     4-byte or 1024 8-byte consecutive needles, finds the tile's first and last segment and each needle's own segment by bounds over
+ *     needle_offsets (equal rows: a multiplication), and searches every needle in its own haystack with a trip count that follows
+ *     the longest haystack among the wave's needles.  One segment with all the needles fills the device; segments without needles
+ *     cost nothing.
+ *   - THE WINDOW: the haystacks of the consecutive segments of a tile are one range of `hay`; where it holds at most `window` keys
+ *     the workgroup copies it into LDS once and every probe of the tile goes there, otherwise the probes go to global memory.
+ *     glu_sorted_search_set_batch_window: keys = 0 (never stage), 16 <= keys <= 32768 / key bytes, or
+ *     GLU_SEARCH_BATCH_WINDOW_DEFAULT: the maximum of the call's key width, 8192 or 4096 keys (DESIGN.md 4.21 on what was and
+ *     what was not measured).  A call checks the value against its own key width.  The window never changes a result.
+ *   - No scratch and no prepare: the calls allocate nothing, only enqueue on `stream` and are capturable from the first call on a
+ *     fresh object.  No atomics, no host synchronisation, nothing that waits for another workgroup; the grid follows from the
+ *     needle count and the needle pointer's alignment, so a captured call replays on any contents (offsets included) and gives the
+ *     same bits every time.  The calls do not touch the object's index scratch or its remembered index: a reuse_index call after a
+ *     batched call still works.
+ *   - glu_sorted_search_last after a batched call: path = GLU_SEARCH_PATH_BATCH, levels = 0, kernels = 0 or 1.
+ *   - OUT OF SCOPE: an index per segment (a few very long rows are served by the loop of single INDEXED calls, which is ahead of
+ *     probing global memory there); a per-segment key type; 64-bit positions. */
+#define GLU_SEARCH_BATCH_WINDOW_DEFAULT 0xFFFFFFFFu
+GLU_API glu_status glu_sorted_search_run_batch_ptr(glu_sorted_search search, const void* hay, size_t hay_count, const void* needles,
+                                                   size_t needle_count, size_t num_partitions, glu_key_type key_type,
+                                                   uint32_t* out_lower, uint32_t* out_upper, void* stream);
+GLU_API glu_status glu_sorted_search_run_batch_offsets_ptr(glu_sorted_search search, const void* hay, size_t hay_total,
+                                                           const uint32_t* hay_offsets, const void* needles, size_t needle_total,
+                                                           const uint32_t* needle_offsets, size_t num_segments, glu_key_type key_type,
+                                                           uint32_t* out_lower, uint32_t* out_upper, void* stream);
+GLU_API glu_status glu_sorted_search_set_batch_window(glu_sorted_search search, uint32_t keys);
+/* Host only, no device, pure: tile = needles per tile (2048 or 1024), tiles = ceil(needle_total / tile), the tiles of needle_total
+ * needles that start on a 16-byte boundary (a needle array that starts behind one can take one tile more), window_keys_used = the
+ * window in keys (window_keys: 0, a value in the range of the key width, or GLU_SEARCH_BATCH_WINDOW_DEFAULT), kernels = 0 or 1.
+ * Any pointer may be NULL. */
+GLU_API glu_status glu_sorted_search_plan_batch(size_t needle_total, glu_key_type key_type, uint32_t window_keys, uint32_t* tile,
+                                                uint32_t* tiles, uint32_t* window_keys_used, uint32_t* kernels);
 
 /* ---- merge (not in the reference): two sorted arrays of keys, with or without 4-byte values, into one sorted array, stable, on
  * the device and on the caller's stream.  The update of a sorted table by a sorted batch, and the step between the batched or the
