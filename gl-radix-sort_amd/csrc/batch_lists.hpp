@@ -76,6 +76,26 @@ inline BatchListsLayout batch_lists_layout(const BatchClasses& cls, size_t total
 }
 
 #ifdef __HIPCC__
+#define GLU_BATCH_FN __host__ __device__ __forceinline__
+#else
+#define GLU_BATCH_FN inline // (a host compiler: the test programs)
+#endif
+
+// The clamp of a segment, on the two offsets already loaded: [b, e) where b <= e <= total, else the empty segment at b.  Plain C++,
+// so that a host program (tests/test_histogram_batch_walk.py) walks whole calls through the rule the kernels use.
+template<typename I>
+GLU_BATCH_FN void batch_clamp_segment(uint32_t b, uint32_t e, const uint32_t& total, I& begin, I& len)
+{
+    if (e < b || e > total) e = b;
+    begin = b;
+    len = e - b;
+}
+
+// Whether the run of `nchunks` chunk slots from `got` on lies inside a chunk list of `capacity` slots: only then is a long segment
+// listed, so that every listed segment has all its chunks (the batched reduce's rule; the batched histogram's binning calls this).
+GLU_BATCH_FN bool batch_chunk_run_fits(uint64_t got, uint32_t nchunks, uint32_t capacity) { return got + nchunks <= capacity; }
+
+#ifdef __HIPCC__
 // Element range of segment `seg` of device offsets, which the host cannot check: a segment that ends below its begin or beyond
 // `total` is empty, so no kernel reads or writes outside [0, total) whatever the array holds.
 // (begin, len: 32 bits wide in the sort, 64 in the reduce and the scan.  `total` by reference: a caller that keeps it in a struct of
@@ -84,10 +104,8 @@ template<typename I>
 __device__ __forceinline__ void batch_offsets_segment(const uint32_t* offsets, const uint32_t& total, uint32_t seg, I& begin, I& len)
 {
     const uint32_t b = offsets[seg];
-    uint32_t e = offsets[seg + 1];
-    if (e < b || e > total) e = b;
-    begin = b;
-    len = e - b;
+    const uint32_t e = offsets[seg + 1];
+    batch_clamp_segment(b, e, total, begin, len);
 }
 
 // How many entries of a list a kernel walks: the count the binning kernel wrote, never more than the list holds.
@@ -122,6 +140,40 @@ __device__ __forceinline__ void batch_append(int cls, uint32_t seg, uint32_t lan
             const uint32_t at = first + __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
             if (at < layout.capacity[c]) lists[layout.start[c] + at] = seg; // (cannot overflow with non-decreasing offsets)
         }
+    }
+}
+
+// Binning, the long class of the wide form: every lane of a wave comes here, `is_long` where its segment `seg` is longer than the
+// workgroup class and has `nchunks` chunks.  What reduce_batch_bin_kernel spells out in place, for kernels that bin by themselves
+// (the batched histogram's): a long segment takes its run of chunk slots with one 64-bit atomic and its place in the long list only
+// if the whole run lies inside the chunk list (batch_chunk_run_fits); every slot below the chunk list's capacity gets its entry,
+// written by the whole wave.  Non-decreasing offsets always fit; of overlapping segments those that do not get no result.
+__device__ __forceinline__ void batch_append_long(bool is_long, uint32_t seg, uint32_t nchunks, uint32_t lane, const BatchListsLayout& layout,
+                                                  uint32_t* __restrict__ counts, uint32_t* __restrict__ lists)
+{
+    const uint32_t capacity = layout.capacity[BATCH_LIST_CHUNKS];
+    uint32_t slot = capacity;
+    if (is_long)
+    {
+        const unsigned long long got = atomicAdd(reinterpret_cast<unsigned long long*>(counts + kBatchCountChunks), (unsigned long long) nchunks);
+        if (got < capacity) slot = (uint32_t) got;
+        if (batch_chunk_run_fits(got, nchunks, capacity))
+        {
+            const uint32_t at = atomicAdd(&counts[kBatchCountLong], 1u);
+            if (at < layout.capacity[BATCH_LIST_LONG]) reinterpret_cast<uint2*>(lists + layout.start[BATCH_LIST_LONG])[at] = make_uint2(seg, slot);
+        }
+    }
+    uint64_t m = __ballot(is_long);
+    while (m) // wave-uniform
+    {
+        const int src = __ffsll((unsigned long long) m) - 1;
+        m &= m - 1;
+        const uint32_t s_seg = (uint32_t) __shfl((int) seg, src);
+        const uint32_t s_slot = (uint32_t) __shfl((int) slot, src);
+        const uint32_t s_n = (uint32_t) __shfl((int) nchunks, src);
+        uint2* chunks = reinterpret_cast<uint2*>(lists + layout.start[BATCH_LIST_CHUNKS]);
+        for (uint32_t c = lane; c < s_n; c += 64u)
+            if ((uint64_t) s_slot + c < capacity) chunks[s_slot + c] = make_uint2(s_seg, c);
     }
 }
 #endif // __HIPCC__

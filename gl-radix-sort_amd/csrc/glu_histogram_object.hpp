@@ -1,8 +1,10 @@
 // glu_histogram_object.hpp -- the Histogram object behind glu::Histogram (glu_histogram.hip owns its life and its calls).  The plan
-// of a call is histogram_bins.hpp's hist_plan.
+// of a call is histogram_bins.hpp's hist_plan, of a batched call its hist_batch_plan.
 #pragma once
 
+#include "glu_batch_host.hpp"
 #include "glu_tile_host.hpp"
+#include "histogram_batch_walk.hpp"
 #include "histogram_bins.hpp"
 
 struct glu_histogram_s
@@ -13,7 +15,16 @@ struct glu_histogram_s
     {
         uint32_t path = 0, groups = 0, kernels = 0;
     } last;
-    void release() { partial.release(); }
+    // batched calls: the list image of a call with device offsets (batch_lists.hpp), the rows of the chunks of the long segments,
+    // the segments per class of the last one (glu_histogram_read_batch)
+    glu_hip::host::Scratch batch_lists, batch_partial;
+    glu_hip::host::LastBatch last_batch;
+    void release()
+    {
+        partial.release();
+        batch_lists.release();
+        batch_partial.release();
+    }
 };
 
 namespace glu_hip

@@ -21,7 +21,8 @@
 //   glu_sorted_search.hip     sorted search: lower and upper bounds of many needles in a sorted haystack (sorted_search_kernels.hpp),
 //                             and every segment's needles in its own haystack (sorted_search_batch_kernels.hpp over search_batch_walk.hpp)
 //   glu_merge.hip             merge: two sorted arrays of keys and values into one, stable (merge_kernels.hpp over merge_path.hpp)
-//   glu_histogram.hip         histogram: counts per bin over even bins or sorted edges (histogram_kernels.hpp over histogram_bins.hpp)
+//   glu_histogram.hip         histogram: counts per bin over even bins or sorted edges (histogram_kernels.hpp over histogram_bins.hpp),
+//                             and every segment's counts in a row of its own (histogram_batch_kernels.hpp over histogram_batch_walk.hpp)
 //   glu_expand.hip            expand: segment, rank and item per element from the offsets (expand_kernels.hpp over expand_path.hpp)
 //   glu_gather.hip            gather and scatter: items fetched or placed by device indices (gather_kernels.hpp over gather_walk.hpp)
 //   glu_top_k.hip             top-k: the k smallest or largest keys and their indices by a radix select (topk_kernels.hpp over topk_pick.hpp)

@@ -31,7 +31,8 @@ enum
 enum
 {
     HIST_PATH_LDS = 0,
-    HIST_PATH_GLOBAL = 1
+    HIST_PATH_GLOBAL = 1,
+    HIST_PATH_BATCH = 2 // a batched call (the batched plan below); what glu_histogram_last reports for it
 };
 
 // ---- even bins over uint32 / int32: bin = floor((x - lo) / W), exactly ---------------------------------------------------------
@@ -171,6 +172,63 @@ inline HistPlan hist_plan(uint64_t count, uint32_t bins, uint32_t key_bytes, int
         p.kernels = (accumulate ? 0u : 1u) + (count ? 1u : 0u);
         p.scratch_bytes = 0;
     }
+    return p;
+}
+
+// ---- the batched plan (histogram_batch_kernels.hpp: every segment of an array counted into a row of its own) --------------------
+// Three classes by the length of a segment, drawn here and nowhere else (glu_histogram_plan_batch reports them):
+//   wave   up to wave_limit samples and bins <= 2048: a wave per segment with a table of its own, four to a workgroup (32 KiB).
+//          8 KiB of samples.  With more bins the class is empty and its segments are the block class's.
+//   block  up to block_limit = one chunk: a workgroup per segment, the table of the single call.
+//   long   cut into chunks of max(512 KiB of samples, 64 samples per bin): a chunk's partial row of bins * 4 bytes is then at most
+//          1/16 of a byte per sample of the chunk, and a batch has at most 2 * (total / chunk) chunks (hist_batch_slots): the
+//          scratch of a prepared batch stays at or below total / 8 bytes.
+// Each value was held against half and twice of the starting values (4 KiB, 256 KiB, one chunk) on the device, and 8 KiB and 512 KiB
+// won (profiles/histogram_batch/constants.txt); against twice of THESE they were not held: provisional upwards.
+// (A tuning build of glu_histogram.hip sets one of the three macros; the library is built without them.)
+#ifndef GLU_HIST_BATCH_WAVE_BYTES
+#define GLU_HIST_BATCH_WAVE_BYTES 8192
+#endif
+#ifndef GLU_HIST_BATCH_CHUNK_BYTES
+#define GLU_HIST_BATCH_CHUNK_BYTES (1u << 19)
+#endif
+#ifndef GLU_HIST_BATCH_BLOCK_BYTES
+#define GLU_HIST_BATCH_BLOCK_BYTES GLU_HIST_BATCH_CHUNK_BYTES
+#endif
+constexpr uint32_t kHistBatchWaveBytes = GLU_HIST_BATCH_WAVE_BYTES;   // longest segment of the wave class, in bytes of samples
+constexpr uint32_t kHistBatchWaveBins = 2048;                         // most bins of the wave class: four tables of them are 32 KiB
+constexpr uint32_t kHistBatchWaves = 4;                               // waves (segments at a time) of a workgroup of the wave class
+constexpr uint32_t kHistBatchChunkBytes = GLU_HIST_BATCH_CHUNK_BYTES; // a chunk of the long class, in bytes of samples, at the least
+constexpr uint32_t kHistBatchBlockBytes = GLU_HIST_BATCH_BLOCK_BYTES; // longest segment of the block class: one chunk
+constexpr uint32_t kHistBatchChunkPerBin = 64;                        // ... and both in samples per bin, at the least
+
+constexpr uint32_t hist_batch_wave_limit(uint32_t bins, uint32_t key_bytes) { return bins <= kHistBatchWaveBins ? kHistBatchWaveBytes / key_bytes : 0u; }
+constexpr uint32_t hist_batch_at_least_per_bin(uint32_t samples, uint32_t bins)
+{
+    return samples > kHistBatchChunkPerBin * bins ? samples : kHistBatchChunkPerBin * bins;
+}
+constexpr uint32_t hist_batch_chunk(uint32_t bins, uint32_t key_bytes) { return hist_batch_at_least_per_bin(kHistBatchChunkBytes / key_bytes, bins); }
+constexpr uint32_t hist_batch_block_limit(uint32_t bins, uint32_t key_bytes)
+{
+    return hist_batch_at_least_per_bin(kHistBatchBlockBytes / key_bytes, bins);
+}
+
+struct HistBatchPlan
+{
+    uint32_t path, workgroups, wave_limit, block_limit, chunk; // path: 0 = empty, 1 = wave, 2 = block, 3 = long
+    size_t scratch_bytes_per_chunk;
+};
+
+// one segment of `count` samples (bins <= kHistLdsBins: the caller)
+inline HistBatchPlan hist_batch_plan(uint64_t count, uint32_t bins, uint32_t key_bytes)
+{
+    HistBatchPlan p;
+    p.wave_limit = hist_batch_wave_limit(bins, key_bytes);
+    p.block_limit = hist_batch_block_limit(bins, key_bytes);
+    p.chunk = hist_batch_chunk(bins, key_bytes);
+    p.scratch_bytes_per_chunk = (size_t) bins * sizeof(uint32_t);
+    p.path = count == 0 ? 0u : count <= p.wave_limit ? 1u : count <= p.block_limit ? 2u : 3u;
+    p.workgroups = p.path == 3 ? (uint32_t) ((count + p.chunk - 1) / p.chunk) : p.path ? 1u : 0u;
     return p;
 }
 

@@ -56,6 +56,79 @@ namespace glu
             bincount((const uint32_t*) ids.device_ptr(), count, bins, (uint32_t*) out_counts.device_ptr(), accumulate);
         }
 
+        /// Batched histogram (glu_histogram_run_batch_*_ptr in glu_hip.h): out_counts[s * bins + b] = the samples of segment s in
+        /// bin b, by the rule of even() / edges(), every segment in one call.  Scratch for batches of up to `total` samples in up
+        /// to `num_segments` segments over `bins` bins: they then allocate nothing and can be captured.
+        void prepare_batch(size_t total, size_t num_segments, size_t bins)
+        {
+            GLU_CHECK_STATUS(glu_histogram_prepare_batch(m_impl, total, num_segments, bins));
+        }
+
+        /// `num_partitions` adjacent partitions of `count` samples, `bins` even bins over [lo, hi) for all of them.
+        template<typename T>
+        void even_batch(const T* device_samples, size_t count, size_t num_partitions, T lo, T hi, size_t bins, uint32_t* device_out_counts,
+                        bool accumulate = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_batch_even_ptr(m_impl, device_samples, count, num_partitions, key_type_of<T>(), &lo, &hi, bins,
+                                                              device_out_counts, accumulate ? 1 : 0, stream));
+        }
+
+        /// The segments [offsets[s], offsets[s + 1]) of `total` samples; `device_offsets`: num_segments + 1 uint32, only read.
+        template<typename T>
+        void even_batch_offsets(const T* device_samples, size_t total, const uint32_t* device_offsets, size_t num_segments, T lo, T hi,
+                                size_t bins, uint32_t* device_out_counts, bool accumulate = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_batch_offsets_even_ptr(m_impl, device_samples, total, device_offsets, num_segments,
+                                                                      key_type_of<T>(), &lo, &hi, bins, device_out_counts, accumulate ? 1 : 0,
+                                                                      stream));
+        }
+
+        /// Partitions over the one array of `bins + 1` device edges.
+        template<typename T>
+        void edges_batch(const T* device_samples, size_t count, size_t num_partitions, const T* device_edges, size_t bins,
+                         uint32_t* device_out_counts, bool accumulate = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_batch_edges_ptr(m_impl, device_samples, count, num_partitions, key_type_of<T>(), device_edges, bins,
+                                                               device_out_counts, accumulate ? 1 : 0, stream));
+        }
+
+        /// Segments of device offsets over the one array of `bins + 1` device edges.
+        template<typename T>
+        void edges_batch_offsets(const T* device_samples, size_t total, const uint32_t* device_offsets, size_t num_segments,
+                                 const T* device_edges, size_t bins, uint32_t* device_out_counts, bool accumulate = false, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_histogram_run_batch_offsets_edges_ptr(m_impl, device_samples, total, device_offsets, num_segments,
+                                                                       key_type_of<T>(), device_edges, bins, device_out_counts,
+                                                                       accumulate ? 1 : 0, stream));
+        }
+
+        /// out_counts[p * bins + v] = the ids of partition p equal to v, v < bins.
+        void bincount_batch(const uint32_t* device_ids, size_t count, size_t num_partitions, size_t bins, uint32_t* device_out_counts,
+                            bool accumulate = false, void* stream = nullptr)
+        {
+            even_batch<uint32_t>(device_ids, count, num_partitions, 0u, (uint32_t) bins, bins, device_out_counts, accumulate, stream);
+        }
+
+        /// ... of the segments of device offsets.
+        void bincount_batch_offsets(const uint32_t* device_ids, size_t total, const uint32_t* device_offsets, size_t num_segments, size_t bins,
+                                    uint32_t* device_out_counts, bool accumulate = false, void* stream = nullptr)
+        {
+            even_batch_offsets<uint32_t>(device_ids, total, device_offsets, num_segments, 0u, (uint32_t) bins, bins, device_out_counts, accumulate,
+                                         stream);
+        }
+
+        /// What the last batched call did with its segments (glu_histogram_read_batch; synchronise its stream first).
+        struct BatchClasses
+        {
+            uint32_t wave_segments = 0, block_segments = 0, long_segments = 0;
+        };
+        [[nodiscard]] BatchClasses read_batch() const
+        {
+            BatchClasses r;
+            GLU_CHECK_STATUS(glu_histogram_read_batch(m_impl, &r.wave_segments, &r.block_segments, &r.long_segments));
+            return r;
+        }
+
         /// What a call with these counts does (glu_histogram_plan; host only, no device needed).
         struct Plan
         {

@@ -152,6 +152,13 @@ SYMBOLS = [
     ("glu_histogram_run_edges_ptr", _int, [_vp, _vp, _sz, _int, _vp, _sz, _vp, _int, _vp]),
     ("glu_histogram_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_histogram_last", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_histogram_run_batch_even_ptr", _int, [_vp, _vp, _sz, _sz, _int, _vp, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_run_batch_offsets_even_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_run_batch_edges_ptr", _int, [_vp, _vp, _sz, _sz, _int, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_run_batch_offsets_edges_ptr", _int, [_vp, _vp, _sz, _vp, _sz, _int, _vp, _sz, _vp, _int, _vp]),
+    ("glu_histogram_prepare_batch", _int, [_vp, _sz, _sz, _sz]),
+    ("glu_histogram_plan_batch", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
+    ("glu_histogram_read_batch", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_expand_create", _int, [_P(_vp)]),
     ("glu_expand_destroy", _int, [_vp]),
     ("glu_expand_prepare", _int, [_vp, _sz, _sz]),
@@ -439,6 +446,21 @@ def plan_histogram(count, bins, key_type="uint32", mode="even"):
     check(lib().glu_histogram_plan(count, bins, KEY_TYPES[key_type], HISTOGRAM_MODES.get(mode, mode), ctypes.byref(a), ctypes.byref(b),
                                    ctypes.byref(c), ctypes.byref(d), ctypes.byref(e), ctypes.byref(f)))
     return a.value, b.value, c.value, d.value, e.value, f.value
+
+
+HistogramPath_Batch = 2
+
+
+def plan_histogram_batch(count, bins, key_type="uint32", mode="even"):
+    """(path, workgroups, (wave_limit, block_limit), chunk, scratch_bytes_per_chunk) of one segment of `count` samples in a batched
+    histogram over `bins` bins (glu_histogram_plan_batch; host only): path 0 = empty, 1 = a wave per segment, 2 = a workgroup per
+    segment, 3 = cut into chunks (workgroups = their number); the limits of the wave class (0 where bins > 2048) and of the block
+    class in samples, the samples of a chunk, and the bytes a chunk's partial row takes in the object's scratch."""
+    a, b, d, e = _u32(), _u32(), _u32(), _sz()
+    c = (_u32 * 2)()
+    check(lib().glu_histogram_plan_batch(count, bins, KEY_TYPES[key_type], HISTOGRAM_MODES.get(mode, mode), ctypes.byref(a), ctypes.byref(b),
+                                         c, ctypes.byref(d), ctypes.byref(e)))
+    return a.value, b.value, (c[0], c[1]), d.value, e.value
 
 
 def plan_expand(total, num_segments):
@@ -878,6 +900,13 @@ class Histogram(_Handle):
         floats rounded to the sample's type (for float32 samples lo = 0.1 means np.float32(0.1), which the kernels widen to double).
         Integers: (hi - lo) / bins a whole number, the bin exact; floats: min(uint32((double(x) - lo) * (bins / (hi - lo))),
         bins - 1).  lo = 0, hi = bins over uint32 is bincount.  Pointers are device pointers (glu_histogram_run_even_ptr)."""
+        lo_v, hi_v = self._bounds(lo, hi, key_type)
+        check(lib().glu_histogram_run_even_ptr(self._h, _vp(samples_ptr), count, KEY_TYPES[key_type], ctypes.byref(lo_v), ctypes.byref(hi_v),
+                                               bins, _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+
+    @staticmethod
+    def _bounds(lo, hi, key_type):
+        """lo and hi as one value each of the sample's type, for the host pointers of the even-bins calls."""
         c = _HISTOGRAM_BOUNDS[key_type]
         try:
             lo_v, hi_v = c(lo), c(hi)
@@ -887,8 +916,7 @@ class Histogram(_Handle):
         # the type does not hold is refused, not wrapped)
         if key_type in ("uint32", "int32", "uint64", "int64") and (lo_v.value != lo or hi_v.value != hi):
             raise GluError(GLU_ERROR_INVALID_ARGUMENT, "lo or hi is not a value of %s: %r, %r" % (key_type, lo, hi))
-        check(lib().glu_histogram_run_even_ptr(self._h, _vp(samples_ptr), count, KEY_TYPES[key_type], ctypes.byref(lo_v), ctypes.byref(hi_v),
-                                               bins, _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+        return lo_v, hi_v
 
     def run_edges_ptr(self, samples_ptr, count, edges_ptr, bins, out_counts_ptr, key_type="uint32", accumulate=False, stream=None):
         """Bins between the bins + 1 non-decreasing DEVICE edges of the sample's type: bin b counts edges[b] <= x < edges[b + 1], floats
@@ -901,6 +929,45 @@ class Histogram(_Handle):
         a, b, c = _u32(), _u32(), _u32()
         check(lib().glu_histogram_last(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def prepare_batch(self, total, num_segments, bins):
+        """Scratch for batched calls of up to `total` samples in up to `num_segments` segments over `bins` bins: they allocate nothing
+        (capturable) (glu_histogram_prepare_batch)."""
+        check(lib().glu_histogram_prepare_batch(self._h, total, num_segments, bins))
+
+    def run_batch_even_ptr(self, samples_ptr, count, num_partitions, lo, hi, bins, out_counts_ptr, key_type="uint32", accumulate=False,
+                           stream=None):
+        """out_counts[p * bins + b] = the samples of partition p, [p * count, (p + 1) * count), in even bin b over [lo, hi): run_even_ptr's
+        rule for every partition, in one call (glu_histogram_run_batch_even_ptr)."""
+        lo_v, hi_v = self._bounds(lo, hi, key_type)
+        check(lib().glu_histogram_run_batch_even_ptr(self._h, _vp(samples_ptr), count, num_partitions, KEY_TYPES[key_type], ctypes.byref(lo_v),
+                                                     ctypes.byref(hi_v), bins, _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+
+    def run_batch_offsets_even_ptr(self, samples_ptr, total, offsets_ptr, num_segments, lo, hi, bins, out_counts_ptr, key_type="uint32",
+                                   accumulate=False, stream=None):
+        """The same for the segments [offsets[s], offsets[s + 1]) of `total` samples; `offsets` is a device array of num_segments + 1
+        uint32, only read (glu_histogram_run_batch_offsets_even_ptr)."""
+        lo_v, hi_v = self._bounds(lo, hi, key_type)
+        check(lib().glu_histogram_run_batch_offsets_even_ptr(self._h, _vp(samples_ptr), total, _vp(offsets_ptr), num_segments, KEY_TYPES[key_type],
+                                                             ctypes.byref(lo_v), ctypes.byref(hi_v), bins, _vp(out_counts_ptr),
+                                                             1 if accumulate else 0, _vp(stream)))
+
+    def run_batch_edges_ptr(self, samples_ptr, count, num_partitions, edges_ptr, bins, out_counts_ptr, key_type="uint32", accumulate=False,
+                            stream=None):
+        """Every partition of `count` samples over the one device array of bins + 1 edges (glu_histogram_run_batch_edges_ptr)."""
+        check(lib().glu_histogram_run_batch_edges_ptr(self._h, _vp(samples_ptr), count, num_partitions, KEY_TYPES[key_type], _vp(edges_ptr), bins,
+                                                      _vp(out_counts_ptr), 1 if accumulate else 0, _vp(stream)))
+
+    def run_batch_offsets_edges_ptr(self, samples_ptr, total, offsets_ptr, num_segments, edges_ptr, bins, out_counts_ptr, key_type="uint32",
+                                    accumulate=False, stream=None):
+        """Every segment of device offsets over the one device array of bins + 1 edges (glu_histogram_run_batch_offsets_edges_ptr)."""
+        check(lib().glu_histogram_run_batch_offsets_edges_ptr(self._h, _vp(samples_ptr), total, _vp(offsets_ptr), num_segments,
+                                                              KEY_TYPES[key_type], _vp(edges_ptr), bins, _vp(out_counts_ptr),
+                                                              1 if accumulate else 0, _vp(stream)))
+
+    def read_batch(self):
+        """{wave, block, long}: segments each class of the last batched call took (glu_histogram_read_batch); synchronise first."""
+        return _read_batch(lib().glu_histogram_read_batch, self._h)
 
 
 class Expand(_Handle):

@@ -987,7 +987,8 @@ enum
 enum
 {
     GLU_HISTOGRAM_PATH_LDS = 0,
-    GLU_HISTOGRAM_PATH_GLOBAL = 1
+    GLU_HISTOGRAM_PATH_GLOBAL = 1,
+    GLU_HISTOGRAM_PATH_BATCH = 2 /* a batched call (below) */
 };
 /* Not in the reference. */
 GLU_API glu_status glu_histogram_create(glu_histogram* out);
@@ -1013,6 +1014,72 @@ GLU_API glu_status glu_histogram_plan(size_t count, size_t bins, glu_key_type ke
 /* Not in the reference.  What the host enqueued in the object's last run (no device read): the path, the workgroups of the counting
  * kernel and the number of kernels. */
 GLU_API glu_status glu_histogram_last(glu_histogram histogram, uint32_t* path, uint32_t* groups, uint32_t* kernels);
+
+/* ---- batched histogram (not in the reference): the counts of every segment of an array in one call, on the existing object.
+ * out_counts[s * bins + b] = the samples of segment s that fall into bin b; a sample gets its bin by EXACTLY the rule of the single
+ * call above.  Per-group distributions after sort -> key runs, a per-row bincount, the per-node feature histograms of tree learners.
+ *   - EVEN BINS (glu_histogram_run_batch_even_ptr, _batch_offsets_even_ptr): the same lo, hi and bins for all segments; the types and
+ *     argument rules of glu_histogram_run_even_ptr, integers exact and floats in double.  EDGES (_batch_edges_ptr,
+ *     _batch_offsets_edges_ptr): ONE device array of bins + 1 edges shared by all segments, all six key types, compared as IEEE values.
+ *   - SEGMENTS.  Equal partitions: segment s is [s * count, (s + 1) * count).  Device offsets: [offsets[s], offsets[s + 1]);
+ *     `offsets` is a DEVICE array of num_segments + 1 uint32, non-decreasing, as glu_key_runs_run_ptr writes it; the host never reads
+ *     it.  A segment that ends below its begin or beyond `total` is empty to every kernel.
+ *   - LIMITS.  1 <= bins <= 8192 in both modes (every table is kept in LDS; there is no batched GLOBAL path).  The total
+ *     (count * num_partitions, or `total`) is below 2^32; num_segments <= 2^24.  Rows are indexed with 64 bits.
+ *   - EVERY entry of the num_segments * bins counts is written; an empty segment gives a row of zeros.  accumulate != 0 adds the
+ *     call's counts modulo 2^32, and the row of an empty segment is then not touched.  num_segments == 0 does nothing.  NULL arrays
+ *     are accepted where nothing would be read or written (samples of an empty batch, everything where num_segments == 0).
+ *   - `samples`, `edges` and `offsets` are only read; nothing outside out_counts[0 .. num_segments * bins) is written.
+ *   - MALFORMED OFFSETS (decreasing, overlapping beyond `total`, out of range): the call stays in bounds: it reads nothing outside
+ *     [0, total) of the samples and writes nothing outside out_counts; the contents of out_counts are then unspecified.  As in the
+ *     batched reduce: the segments that found no room in the lists (overlapping segments can ask for more list entries or chunks than
+ *     an array of `total` samples has) get no result; the rows of the others are right.
+ *   - THREE CLASSES by the length of a segment (glu_histogram_plan_batch states the limits).  Up to wave_limit samples and
+ *     bins <= 2048: a wave per segment with a table of its own in LDS, four waves to the workgroup.  Up to block_limit: a workgroup
+ *     per segment with the table (and the staged edges) of the single call.  Longer: the segment is cut into chunks, a workgroup per
+ *     (segment, chunk) writes its table as a row of partials in the object's scratch, and a sum kernel adds every long segment's rows:
+ *     out = (accumulate ? out : 0) + their sum.  No global atomics on counts anywhere; skew costs nothing.
+ *   - LAUNCHES.  Device offsets: a memset of the list counts, a binning kernel (a lane per segment; it also zeroes the rows of the
+ *     empty segments) and at most four more kernels, whatever the data hold.  Equal partitions: the host picks the class: one or two
+ *     kernels, or only the zeroing where count == 0 (nothing at all under accumulate).
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back, no side stream, and no device allocation once
+ *     glu_histogram_prepare_batch covered the sizes (else grow-only allocation inside the call: not capturable).  Grids follow from
+ *     the counts the host passes, never from the data: a captured call replays on other samples, offsets of the same shape and edges.
+ *     THE SAME INPUT GIVES THE SAME BITS EVERY TIME.
+ *   - GLU_ERROR_INVALID_ARGUMENT with a message that names the argument, and nothing written, for what the single call refuses and
+ *     for: bins > 8192; num_segments > 2^24; a total of 2^32 or more; out_counts overlapping the samples, the edges or the offsets;
+ *     64-bit integer samples with even bins; a NULL or misaligned offsets array.
+ *   - glu_histogram_last then reports GLU_HISTOGRAM_PATH_BATCH, groups 0 and the number of kernels enqueued.
+ *   - OUT OF SCOPE: per-segment lo, hi or edges; more than 8192 bins per segment; weights and 64-bit counts. */
+/* Not in the reference.  The contract above, even bins over equal partitions.  Enqueues on `stream` (NULL: the library's queue). */
+GLU_API glu_status glu_histogram_run_batch_even_ptr(glu_histogram histogram, const void* samples, size_t count, size_t num_partitions,
+                                                    glu_key_type key_type, const void* lo, const void* hi, size_t bins, uint32_t* out_counts,
+                                                    int accumulate, void* stream);
+/* Not in the reference.  The contract above, even bins over device offsets. */
+GLU_API glu_status glu_histogram_run_batch_offsets_even_ptr(glu_histogram histogram, const void* samples, size_t total, const uint32_t* offsets,
+                                                            size_t num_segments, glu_key_type key_type, const void* lo, const void* hi, size_t bins,
+                                                            uint32_t* out_counts, int accumulate, void* stream);
+/* Not in the reference.  The contract above, sorted edges over equal partitions. */
+GLU_API glu_status glu_histogram_run_batch_edges_ptr(glu_histogram histogram, const void* samples, size_t count, size_t num_partitions,
+                                                     glu_key_type key_type, const void* edges, size_t bins, uint32_t* out_counts, int accumulate,
+                                                     void* stream);
+/* Not in the reference.  The contract above, sorted edges over device offsets. */
+GLU_API glu_status glu_histogram_run_batch_offsets_edges_ptr(glu_histogram histogram, const void* samples, size_t total, const uint32_t* offsets,
+                                                             size_t num_segments, glu_key_type key_type, const void* edges, size_t bins,
+                                                             uint32_t* out_counts, int accumulate, void* stream);
+/* Not in the reference.  Grow-only scratch (the segment lists and the partial rows of the long segments) for batched calls of up to
+ * `total` samples in up to `num_segments` segments over `bins` bins, of any key type, mode and form: after it such a call allocates
+ * nothing (and can be captured).  The partial rows take at most total / 8 bytes. */
+GLU_API glu_status glu_histogram_prepare_batch(glu_histogram histogram, size_t total, size_t num_segments, size_t bins);
+/* Not in the reference.  Host only, no device, pure: what one segment of `count` samples does in a batched call.  path = 0 (empty),
+ * 1 (wave class), 2 (block class) or 3 (long class); workgroups = 0, 1, 1 or the chunks of the segment; class_limits[0] = wave_limit
+ * = 8 KiB of samples, or 0 where bins > 2048; class_limits[1] = block_limit = chunk; chunk = max(512 KiB of samples, 64 samples per
+ * bin); scratch_bytes_per_chunk = bins * 4.  Any pointer may be NULL. */
+GLU_API glu_status glu_histogram_plan_batch(size_t count, size_t bins, glu_key_type key_type, int mode, uint32_t* path, uint32_t* workgroups,
+                                            uint32_t* class_limits, uint32_t* chunk, size_t* scratch_bytes_per_chunk);
+/* Not in the reference.  Segments per class of the object's last batched call: the host's own numbers for equal partitions, else the
+ * counts the binning kernel left on the device (synchronise the call's stream first; this call reads them back). */
+GLU_API glu_status glu_histogram_read_batch(glu_histogram histogram, uint32_t* wave_segments, uint32_t* block_segments, uint32_t* long_segments);
 
 /* ---- expand (not in the reference): from the offsets of segments back to the elements: for every element the segment that holds
  * it, its rank inside that segment and the segment's item, on the device and on the caller's stream.  The inverse of key runs
