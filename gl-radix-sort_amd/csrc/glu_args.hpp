@@ -141,5 +141,25 @@ inline void store(T* out, V value)
 {
     if (out) *out = (T) value;
 }
+
+// ---- GLU_HIP_SCRATCH_FILL, the test switch of Scratch::reserve (glu_host.hpp): `text` is the variable as it stands.  Unset or
+// empty: *byte = -1, nothing is filled.  A decimal or 0x integer 0 .. 255: that byte.  Anything else refuses the call that grows.
+inline glu_status check_scratch_fill(const char* text, int* byte)
+{
+    *byte = -1;
+    if (!text || !*text) return GLU_OK;
+    long value = 0;
+    int digits = 0;
+    const bool hex = text[0] == '0' && (text[1] == 'x' || text[1] == 'X');
+    for (const char* c = text + (hex ? 2 : 0); *c && value <= 255; c++, digits++)
+    {
+        const int d = *c >= '0' && *c <= '9' ? *c - '0' : hex && *c >= 'a' && *c <= 'f' ? *c - 'a' + 10 : hex && *c >= 'A' && *c <= 'F' ? *c - 'A' + 10 : -1;
+        if (d < 0) return fail(GLU_ERROR_INVALID_ARGUMENT, "GLU_HIP_SCRATCH_FILL must be an integer 0 .. 255 (got \"%s\")", text);
+        value = value * (hex ? 16 : 10) + d;
+    }
+    if (digits == 0 || value > 255) return fail(GLU_ERROR_INVALID_ARGUMENT, "GLU_HIP_SCRATCH_FILL must be an integer 0 .. 255 (got \"%s\")", text);
+    *byte = (int) value;
+    return GLU_OK;
+}
 } // namespace host
 } // namespace glu_hip

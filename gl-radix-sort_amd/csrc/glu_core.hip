@@ -1,5 +1,6 @@
 // glu_core.hip -- libglu_hip.so's errors, device, buffers and timer (the C ABI of include/glu_hip.h; gfx950 only, no CPU fallback),
 // and the definitions behind glu_host.hpp.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <unordered_map>
@@ -33,6 +34,22 @@ glu_status fail(glu_status code, const char* fmt, ...)
     return code;
 }
 
+namespace
+{
+std::atomic<size_t> g_scratch_filled{0}; // bytes filled under GLU_HIP_SCRATCH_FILL by this process
+}
+
+glu_status fill_new_scratch(void* ptr, size_t bytes)
+{
+    int byte = -1;
+    GLU_TRY(check_scratch_fill(glu_env("GLU_HIP_SCRATCH_FILL"), &byte));
+    if (byte < 0) return GLU_OK;
+    // the whole size, and complete before anything the caller enqueues on any stream
+    HIP_TRY(hipMemset(ptr, byte, bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    g_scratch_filled += bytes;
+    return GLU_OK;
+}
 
 Device g_dev;
 
@@ -110,6 +127,13 @@ extern "C" {
 
 const char* glu_last_error(void) { return g_last_error.c_str(); }
 const char* glu_version(void) { return "glu_hip 0.6.0 gfx950"; }
+
+glu_status glu_scratch_filled_bytes(size_t* bytes)
+{
+    if (!bytes) return fail(GLU_ERROR_INVALID_ARGUMENT, "bytes is NULL");
+    *bytes = g_scratch_filled.load();
+    return GLU_OK;
+}
 
 glu_status glu_device_count(int* count)
 {

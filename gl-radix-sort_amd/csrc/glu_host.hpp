@@ -103,6 +103,12 @@ struct Buffer
 };
 glu_status lookup(glu_buffer h, Buffer& out, const char* what);
 
+// GLU_HIP_SCRATCH_FILL (a test switch, read at every growth): a new scratch allocation is filled with that byte, 0 .. 255, before
+// anything can be enqueued on it, and its size is added to what glu_scratch_filled_bytes() reads.  What a fresh allocation holds is
+// an input of every kernel that no caller controls; the operators may not depend on it ("Who writes scratch first").
+// Unset: one getenv per growth and nothing else.  Any other value refuses the call that grows, and the object keeps no allocation.
+glu_status fill_new_scratch(void* ptr, size_t bytes);
+
 // grow-only device allocation owned by an operator object
 struct Scratch
 {
@@ -115,6 +121,13 @@ struct Scratch
         ptr = nullptr;
         size = 0;
         HIP_TRY(hipMalloc(&ptr, bytes));
+        const glu_status filled = fill_new_scratch(ptr, bytes);
+        if (filled != GLU_OK)
+        {
+            (void) hipFree(ptr);
+            ptr = nullptr;
+            return filled;
+        }
         size = bytes;
         if (glu_verbose()) fprintf(stderr, "[glu_hip] scratch reallocated to: %zu\n", bytes);
         return GLU_OK;

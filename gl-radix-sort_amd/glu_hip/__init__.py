@@ -41,6 +41,7 @@ _P = ctypes.POINTER
 SYMBOLS = [
     ("glu_last_error", ctypes.c_char_p, []),
     ("glu_version", ctypes.c_char_p, []),
+    ("glu_scratch_filled_bytes", _int, [_P(_sz)]),
     ("glu_device_count", _int, [_P(_int)]),
     ("glu_set_device", _int, [_int]),
     ("glu_device_info", _int, [ctypes.c_char_p, _sz]),
@@ -339,6 +340,14 @@ class ShaderStorageBuffer:
             self.destroy()
         except Exception:
             pass
+
+
+def scratch_filled_bytes():
+    """The bytes of operator scratch this process has filled under GLU_HIP_SCRATCH_FILL (glu_scratch_filled_bytes; host only): 0
+    while the variable was never set.  A test of the switch reads it before and after to show that it was not vacuous."""
+    a = _sz(0)
+    check(lib().glu_scratch_filled_bytes(ctypes.byref(a)))
+    return a.value
 
 
 def plan_finish(count, key_bytes=4):

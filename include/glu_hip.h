@@ -108,6 +108,13 @@ GLU_API glu_status glu_device_synchronize(void);
 /* The library queue as a hipStream_t (void*), for callers that want to enqueue their own work in order. */
 GLU_API glu_status glu_queue(void** stream);
 
+/* Host only, no device.  A test switch: with GLU_HIP_SCRATCH_FILL set to an integer 0 .. 255 (read whenever an operator object's
+ * scratch grows, never inside a call that does not grow), every new scratch allocation is filled with that byte before the call
+ * goes on, so that a test can hold the results apart from what fresh device memory happens to contain.  Any other value is an
+ * invalid-argument error of the call that grows.  *bytes: the bytes filled so far by this process (0 while the variable was never
+ * set), by which such a test shows that it did fill something. */
+GLU_API glu_status glu_scratch_filled_bytes(size_t* bytes);
+
 /* ---- buffers: replaces glu::ShaderStorageBuffer's GL calls (glu/gl_utils.hpp:146-246) ------------- */
 
 /* glCreateBuffers + glBufferStorage(size, NULL)      (gl_utils.hpp:203-205).  size may be 0. */

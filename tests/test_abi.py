@@ -22,7 +22,8 @@ def test_header_declares_the_expected_surface():
     names = declared_symbols()
     assert len(names) == len(set(names)) >= 38
     for needed in ("glu_radix_sort_create", "glu_radix_sort_prepare", "glu_radix_sort_run", "glu_scan_run",
-                   "glu_reduce_run", "glu_buffer_create_with_data", "glu_buffer_read", "glu_timer_begin", "glu_last_error"):
+                   "glu_reduce_run", "glu_buffer_create_with_data", "glu_buffer_read", "glu_timer_begin", "glu_last_error",
+                   "glu_scratch_filled_bytes"):
         assert needed in names
 
 

@@ -3,6 +3,7 @@ segment s, every segment on its own, the input only read.  Expected results come
 oracle.dtype_info applied to every segment's slice, the operator's identity for an empty one.  Inputs are built the way
 test_reduce_every_type_and_operator builds them (float sums that are exact in any order, products of mostly ones), so `==` is the
 check for every type; the floats that do round have a test of their own against math.fsum."""
+import gc
 import math
 import os
 import subprocess
@@ -707,6 +708,7 @@ def test_prepared_batch_allocates_nothing_and_replays_from_a_graph(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(d, offsets)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             red.run_batch_offsets_ptr(kt.data_ptr(), out.data_ptr(), total, ot.data_ptr(), nseg, torch.cuda.current_stream().cuda_stream)
         for rep in range(3):

@@ -3,6 +3,7 @@ its own exclusive `+` scan, in place, everything else left alone.  Expected valu
 in uint64 / float64).  Integer inputs are random words (sums wrap modulo 2^32); float inputs are k x 0.125 with integer k bounded
 per segment so that length x max|k| < 2^24: every partial sum is then exact in float32 in any order, so `==` is the check for
 every type.  Floats that do round have a test of their own against math.fsum.  The class limits are read from plan_scan_batch."""
+import gc
 import os
 import subprocess
 from fractions import Fraction
@@ -486,6 +487,7 @@ def test_prepared_batch_allocates_nothing_and_replays_from_a_graph(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(d, offsets)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             scan.run_batch_offsets_ptr(kt.data_ptr(), total, ot.data_ptr(), nseg, torch.cuda.current_stream().cuda_stream)
         for rep in range(3):

@@ -2,6 +2,7 @@
 of an array sorted on its own, stable, ascending, in place.  Expected results come from numpy: the keys are encoded to their
 unsigned order here in the test and every segment is ordered by np.argsort(kind="stable") (for very many segments by one
 np.lexsort over (encoded key, segment index), which is the same stable order); values are iota, so the stable result is unique."""
+import gc
 import os
 import subprocess
 
@@ -260,6 +261,7 @@ def test_prepared_batch_allocates_nothing_and_replays_from_a_graph(G):
         assert sorter.scratch_size() == size
         ek, ev = expected(keys, vals, offsets)
         assert (kt.cpu().numpy().view(np.uint32) == ek).all() and (vt.cpu().numpy().view(np.uint32) == ev).all()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             sorter.sort_batch_offsets_ptr(kt.data_ptr(), vt.data_ptr(), total, ot.data_ptr(), nseg, "uint32",
                                           torch.cuda.current_stream().cuda_stream)

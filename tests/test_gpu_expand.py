@@ -4,6 +4,7 @@ Every comparison is `==`.  Every array the call writes sits inside an allocation
 it, and is itself filled with poison first, so positions that are not covered are seen to stay untouched; the inputs are checked
 unchanged; last() is checked against plan_expand.  The scheme is that of test_gpu_merge.py."""
 import ctypes
+import gc
 import itertools
 import os
 import subprocess
@@ -307,6 +308,7 @@ def test_prepared_captured_replayed(G):
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         assert ex.last() == G.plan_expand(total, n)[1:3] == (28, 2)
         verify(contents[0])
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for offsets in contents[::-1]:

@@ -4,6 +4,7 @@ bytes fetched or placed by device indices.  The oracle is always numpy on the ho
 it and behind it, and is itself filled with poison first, so entries that must stay untouched are seen to stay untouched; the inputs
 are checked unchanged.  The scheme is that of test_gpu_expand.py."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -520,6 +521,7 @@ def test_captured_replayed(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a call changed the device memory in use"
         verify(contents[0])
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for c in contents[::-1]:

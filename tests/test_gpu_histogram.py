@@ -7,6 +7,7 @@ Every array a call writes sits inside an allocation with poison in front of it a
 the inputs are checked unchanged; last() is checked against plan_histogram; sum(out) is the number of samples in range.  Sizes come
 from plan_histogram.  The scheme is that of test_gpu_merge.py."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -408,6 +409,7 @@ def test_prepared_captured_replayed(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(*data)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for spread in (2 ** 32, 30000, 1000, 2):  # mostly out of range, spread over the global bins, dense, two values

@@ -8,6 +8,7 @@ and every comparison is `==`:
 Every array a call writes sits inside an allocation with 64 bytes of poison in front of it and behind it and is itself filled with
 poison first; the inputs are checked unchanged; read_batch() is checked against plan_histogram_batch and last() against the kernels
 the header states.  Sizes come from plan_histogram_batch.  The scheme is that of test_gpu_histogram.py."""
+import gc
 import os
 import subprocess
 
@@ -446,6 +447,7 @@ def test_a_prepared_call_is_captured_and_replayed_on_other_contents(G):
         call(side.cuda_stream)
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):  # (an allocation inside the call would end the capture with an error)
             call(torch.cuda.current_stream().cuda_stream)
         for trial in range(4):  # (the contents are filled and the graph replayed on the stream of the capture, as everywhere in this suite)

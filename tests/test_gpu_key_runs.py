@@ -3,6 +3,7 @@ key at every head and the number of runs.  Expected values come from numpy: head
 != 0]).  Every array the call writes sits inside an allocation with poison in front of it and behind it, and is itself filled with
 poison first, so that an entry the call must not touch still holds it.  Sizes come from plan_key_runs."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -512,6 +513,7 @@ def test_prepared_captured_replayed(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(keys)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         seen = []

@@ -3,6 +3,7 @@ counting passes on the TOP 16 key bits and one pass that orders every run of equ
 that only if no run is longer than a workgroup's tile, else the four ordinary passes run.  Either way the result is the
 stable sort of glu::RadixSort::operator() (reference glu/RadixSort.hpp:273-334) -- compared bit for bit with the oracle,
 through the C ABI."""
+import gc
 import os
 
 import numpy as np
@@ -709,6 +710,7 @@ def test_one_captured_graph_serves_every_outcome(G):
         vt.copy_(torch.from_numpy(vals.view(np.int32)))
         sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, side.cuda_stream)  # warm-up outside the capture
         side.synchronize()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, torch.cuda.current_stream().cuda_stream)
         for keys, accepted, capacity in inputs:

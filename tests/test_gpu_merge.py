@@ -5,6 +5,7 @@ and the place every output came from are visible.  Every comparison is `==`.  Ev
 with poison in front of it and behind it, and is itself filled with poison first; the inputs are checked unchanged; last() is
 checked against plan_merge.  The scheme is that of test_gpu_sorted_search.py."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -337,6 +338,7 @@ def test_prepared_captured_replayed(G):
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         assert mg.last() == (28, 2)
         verify(*data)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for spread in (2 ** 32, 5000, 3):  # all keys different, many copies of every key, three keys

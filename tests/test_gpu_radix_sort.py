@@ -1,5 +1,6 @@
 """GPU parity tests of the hot path (glu::RadixSort::operator(), reference glu/RadixSort.hpp:273-334), called
 through the C ABI of libglu_hip.so and compared bit-for-bit with the oracle."""
+import gc
 import os
 
 import numpy as np
@@ -858,6 +859,7 @@ def test_sort_is_graph_capturable_and_replayable(G, n, bits):
         vt.copy_(torch.arange(n, dtype=torch.int32))
         sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, side.cuda_stream)  # warm-up outside the capture
         side.synchronize()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, torch.cuda.current_stream().cuda_stream)
         for rep in range(3):
@@ -1103,6 +1105,7 @@ def test_planned_sort_inside_a_captured_graph(G):
         vt.copy_(torch.from_numpy(vals.view(np.int32)))
         sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, side.cuda_stream)
         side.synchronize()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             sorter.run_ptr(kt.data_ptr(), vt.data_ptr(), n, 0, torch.cuda.current_stream().cuda_stream)
         for keys in inputs:

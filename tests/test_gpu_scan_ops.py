@@ -4,6 +4,7 @@ values are scan_ops_cases.py's (exact in any grouping, so `==` is the check; tes
 GPU); floats that do round have tests of their own against exact arithmetic.  Every array lies between guards of poison inside
 its allocation and the whole allocation is compared.  Class limits come from plan_scan_batch."""
 import ctypes
+import gc
 
 import numpy as np
 import pytest
@@ -328,8 +329,9 @@ def test_null_offsets_scan_the_whole_array(G, dt, op, inclusive):
 # ------------------------------------------------------------------------------------------------------------------ by key
 
 
-def test_running_maximum_by_key(G):
-    """run_by_key_ptr with op="max", inclusive=True and an `out` array, on sorted keys with runs of every class, against numpy."""
+def running_maximum_by_key(G, scan, runs):
+    """run_by_key_ptr with op="max", inclusive=True and an `out` array on `scan` (of uint32) and `runs`, objects made by the caller, on
+    sorted keys with runs of every class, against numpy.  Returns (out, read_batch)."""
     import torch
 
     dt, op = 3, "max"
@@ -345,7 +347,6 @@ def test_running_maximum_by_key(G):
     ot = torch.zeros(max_runs + 1, dtype=torch.int32, device="cuda")
     nt = torch.zeros(1, dtype=torch.int32, device="cuda")
     data, out = Array(d, dt), poison_array(dt, count)
-    scan, runs = G.BlellochScan(dt), G.KeyRuns()
     scan.run_by_key_ptr(runs, kt.data_ptr(), data.ptr, count, ot.data_ptr(), max_runs, nt.data_ptr(), stream=stream(), out_ptr=out.ptr, op=op,
                         inclusive=True)
     torch.cuda.synchronize()
@@ -356,6 +357,12 @@ def test_running_maximum_by_key(G):
     assert sc.same_bits(data.result(), d)
     rb = scan.read_batch()
     assert rb["wave"] > 0 and rb["block"] > 0 and rb["long"] > 0
+    return out.result(), rb
+
+
+def test_running_maximum_by_key(G):
+    """run_by_key_ptr with op="max", inclusive=True and an `out` array, on sorted keys with runs of every class, against numpy."""
+    running_maximum_by_key(G, G.BlellochScan(3), G.KeyRuns())
 
 
 # ------------------------------------------------------------------------------------------------------------ graph capture
@@ -388,6 +395,7 @@ def test_a_captured_out_of_place_inclusive_sum_replays_on_new_inputs(G):
         scan.prepare_batch(total, nseg)
         call(side.cuda_stream)  # warm-up (loads the kernels)
         side.synchronize()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for rep in range(2):

@@ -1,5 +1,6 @@
 """GPU parity tests of glu::BlellochScan and glu::Reduce through the C ABI (reference
 test/blelloch_scan_tests.cpp, test/reduce_tests.cpp: same inputs and assertions, + all data types)."""
+import gc
 import numpy as np
 import pytest
 
@@ -343,6 +344,7 @@ def test_scan_captured_into_a_graph_replays_correctly(G):
         side.synchronize()
         expect = np.concatenate([np.zeros(1, np.uint64), np.cumsum(data[:-1], dtype=np.uint64)]).astype(np.uint32)
         assert (t.cpu().numpy().view(np.uint32) == expect).all()
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             scan.run_ptr(t.data_ptr(), n, 1, torch.cuda.current_stream().cuda_stream)
         for rep in range(3):

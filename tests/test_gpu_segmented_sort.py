@@ -1,6 +1,7 @@
 """GPU parity tests of the segmented stable sort (glu_radix_sort_run_segments_ptr): the reference's stable counting pass
 (glu/RadixSort.hpp:142-182) applied per segment, which is the local sort of the sharded sort.  Expected results come
 from the oracle: every segment's pieces laid end to end, stably sorted by the low key bits."""
+import gc
 import numpy as np
 import pytest
 
@@ -179,6 +180,7 @@ def test_segmented_sort_argument_checks(G):
     graph = torch.cuda.CUDAGraph()
     s.prepare_internal_buffers(100)
     with torch.cuda.stream(side):
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             with pytest.raises(G.GluError) as e:
                 s.run_segments_ptr(k.data_ptr(), v.data_ptr(), k2.data_ptr(), v2.data_ptr(), 100, *one, 1, 24,

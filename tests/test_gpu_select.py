@@ -4,6 +4,7 @@ items[idx]; every comparison is `==`, select is exact.  Every array the call wri
 of it and behind it, and is itself filled with poison first, so that an entry the call must not touch still holds it.  Sizes come
 from plan_select."""
 import ctypes
+import gc
 import operator
 import os
 import subprocess
@@ -479,6 +480,7 @@ def test_prepared_captured_replayed(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(data)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         seen = []

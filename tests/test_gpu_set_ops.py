@@ -10,6 +10,7 @@ the place every output came from are visible.  Every comparison is `==`.  Every 
 poison in front of it and behind it, and is itself filled with poison first; the inputs are checked unchanged; last() is checked
 against plan_set_ops.  The scheme is that of test_gpu_merge.py."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -439,6 +440,7 @@ def test_prepared_captured_replayed(G):
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         assert so_u.last() == (28, 4) and so_i.last() == (28, 4)
         verify(*data)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         seen = set()

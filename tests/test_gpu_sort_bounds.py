@@ -370,16 +370,14 @@ def planned_cases():
     return out
 
 
-@pytest.mark.parametrize("shape,kind,place", planned_cases())
-def test_planned_sorts(G, shape, kind, place):
-    """2^22 + 54321 elements with SORT_PAIR_MIN=1 and SORT_FINISH_MIN=1 (and SORT_LARGE_MIN=1: keys-only sorts reach the line kernel at
-    2^25 keys otherwise, and a sort of unaligned arrays the large-tile kernel at 4.7 M pairs).  Shift 0: two paired top-bit passes of the
-    line kernel, then the in-LDS pass in place on the caller's arrays over runs that begin and end at arbitrary elements, with the
-    long-run passes and the few-keys kernel behind it -- or, refused, the ordinary paired passes.  Other shifts: the planned sort of the
-    ordinary large-tile kernel on the same data."""
+PLANNED_OPTIONS = dict(SORT_PAIR_MIN=1, SORT_FINISH_MIN=1, SORT_LARGE_MIN=1)
+
+
+def planned_sort(G, sorter, shape, kind, place):
+    """One planned sort of planned_case(shape, kind) on `sorter`, an object made by the caller under PLANNED_OPTIONS: arrays, guards
+    and reports as test_planned_sorts states them.  Returns (read_finish, read_long_runs, pair roles)."""
     keys, order, want = planned_case(shape, kind)
     key_bytes, with_vals, typed = keys.dtype.itemsize, kind != "u32keys", kind in ("int32", "float32", "float64")
-    sorter = G.RadixSort(options=dict(SORT_PAIR_MIN=1, SORT_FINISH_MIN=1, SORT_LARGE_MIN=1))
     if typed:
         def call(k, v):
             sorter.sort_typed_ptr(k, v, keys.size, keys.dtype.name, stream())
@@ -392,7 +390,7 @@ def test_planned_sorts(G, shape, kind, place):
         # no attempt to end in LDS and no pass paired: both need the line kernel, which these arrays do not get.  (That the large-tile
         # kernel and not the small one takes its place is SORT_LARGE_MIN's doing: no report separates the two.)
         assert fin["attempted"] == 0 and roles == [0] * key_bytes, (fin, roles)
-        return
+        return fin, lr, roles
     assert fin["attempted"] == 1 and fin["accepted"] == want["accepted"], fin
     if not typed:  # (a pass that encodes typed keys on load leads no pair: their ordinary passes pair differently)
         assert roles == [1, 2] * (key_bytes // 2), roles
@@ -409,6 +407,17 @@ def test_planned_sorts(G, shape, kind, place):
     if kind == "u32pairs":
         ek, ev = O.stable_sort_pairs(keys, iota(keys.size))
         assert (ek == keys[order]).all() and (ev == iota(keys.size)[order]).all()
+    return fin, lr, roles
+
+
+@pytest.mark.parametrize("shape,kind,place", planned_cases())
+def test_planned_sorts(G, shape, kind, place):
+    """2^22 + 54321 elements with SORT_PAIR_MIN=1 and SORT_FINISH_MIN=1 (and SORT_LARGE_MIN=1: keys-only sorts reach the line kernel at
+    2^25 keys otherwise, and a sort of unaligned arrays the large-tile kernel at 4.7 M pairs).  Shift 0: two paired top-bit passes of the
+    line kernel, then the in-LDS pass in place on the caller's arrays over runs that begin and end at arbitrary elements, with the
+    long-run passes and the few-keys kernel behind it -- or, refused, the ordinary paired passes.  Other shifts: the planned sort of the
+    ordinary large-tile kernel on the same data."""
+    planned_sort(G, G.RadixSort(options=PLANNED_OPTIONS), shape, kind, place)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. typed keys, bit ranges
@@ -515,20 +524,14 @@ def partition_order(n, shift, bits):
     return np.argsort(digit, kind="stable"), np.bincount(digit, minlength=1 << bits).astype(np.uint32)
 
 
-@pytest.mark.parametrize("place", PARTITION_PLACES, ids=lambda p: "shifts%d.%d.%d.%d" % p)
-@pytest.mark.parametrize("with_histogram", [True, False], ids=["histogram", "no_histogram"])
-@pytest.mark.parametrize("shift,bits", [(24, 8), (13, 5), (31, 1)])
-@pytest.mark.parametrize("n", [200003, (1 << 22) + 5])
-def test_partition(G, n, shift, bits, with_histogram, place):
-    """One counting pass out of place: the sources are only read, the destinations and the digit histogram lie in poison.  (One pass
-    with no plan: no report separates the line kernel, which 2^22 + 5 aligned pairs run, from the kernels the other cases run.)"""
+def partition(G, sorter, n, shift, bits, with_histogram, place):
+    """One partition_ptr call on `sorter`, a profiled object made by the caller: destinations, histogram, sources and guards."""
     keys, vals = uniform_keys(4, n), iota(n)
     order, counts = partition_order(n, shift, bits)
     no_poison(keys, vals)
     sk, sv = Array(keys, place[0]), Array(vals, place[1])
     dk, dv = Array.poisoned(4 * n, place[2]), Array.poisoned(4 * n, place[3])
     hist = Array.poisoned(4 << bits, place[2] & 12)
-    sorter = profiled(G)
     sync()
     sorter.partition_ptr(sk.ptr, sv.ptr, dk.ptr, dv.ptr, n, shift, bits, hist.ptr if with_histogram else None, stream())
     sync()
@@ -538,6 +541,16 @@ def test_partition(G, n, shift, bits, with_histogram, place):
     sv.expect(vals, "source values")
     hist.expect(counts if with_histogram else np.full(1 << bits, 0xA5A5A5A5, dtype=np.uint32), "histogram")
     assert sorter.read_profile()["passes"] == 1
+
+
+@pytest.mark.parametrize("place", PARTITION_PLACES, ids=lambda p: "shifts%d.%d.%d.%d" % p)
+@pytest.mark.parametrize("with_histogram", [True, False], ids=["histogram", "no_histogram"])
+@pytest.mark.parametrize("shift,bits", [(24, 8), (13, 5), (31, 1)])
+@pytest.mark.parametrize("n", [200003, (1 << 22) + 5])
+def test_partition(G, n, shift, bits, with_histogram, place):
+    """One counting pass out of place: the sources are only read, the destinations and the digit histogram lie in poison.  (One pass
+    with no plan: no report separates the line kernel, which 2^22 + 5 aligned pairs run, from the kernels the other cases run.)"""
+    partition(G, profiled(G), n, shift, bits, with_histogram, place)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 7. segmented sort
@@ -557,20 +570,14 @@ def segmented_case(n, key_bits):
     return keys, begin, length, seg, nseg, ek, ev
 
 
-@pytest.mark.parametrize("place", SEG_PLACES, ids=lambda p: "%s%d" % p)
-@pytest.mark.parametrize("key_bits", [0, 16, 32])
-@pytest.mark.parametrize("n", sorted(SEG_SHAPES))
-def test_segmented_sort(G, n, key_bits, place):
-    """run_segments_ptr with all four arrays in poison: below 2^16 elements (copies and a sort per segment), from 2^16 (segmented
-    passes), 700 001 (ending in LDS); and every count with the inputs, the outputs or both 4 and 12 bytes off a 16-byte boundary, which
-    takes the copies whatever the count.  The inputs' contents are unspecified afterwards; their guards must hold."""
+def segmented_sort(G, sorter, n, key_bits, place):
+    """One run_segments_ptr call of segmented_case(n, key_bits) on `sorter`, an object made by the caller.  Returns read_seg_finish."""
     keys, begin, length, seg, nseg, ek, ev = segmented_case(n, key_bits)
     which, shift = place
     s_in, s_out = (shift if which in ("in", "both") else 0), (shift if which in ("out", "both") else 0)
     no_poison(keys, iota(n), ek, ev)
     ik, iv = Array(keys, s_in), Array(iota(n), s_in)
     ok, ov = Array.poisoned(4 * n, s_out), Array.poisoned(4 * n, s_out)
-    sorter = G.RadixSort()
     sync()
     sorter.run_segments_ptr(ik.ptr, iv.ptr, ok.ptr, ov.ptr, n, begin, length, seg, nseg, key_bits, stream())
     sync()
@@ -585,6 +592,17 @@ def test_segmented_sort(G, n, key_bits, place):
         # copies and a sort per segment: never an attempt.  (No report separates the copies from the segmented passes of an aligned call
         # of 2^16 or 300 000 elements that makes no attempt; seg_make_plan decides by the count and the four pointers.)
         assert rep["attempted"] == 0, rep
+    return rep
+
+
+@pytest.mark.parametrize("place", SEG_PLACES, ids=lambda p: "%s%d" % p)
+@pytest.mark.parametrize("key_bits", [0, 16, 32])
+@pytest.mark.parametrize("n", sorted(SEG_SHAPES))
+def test_segmented_sort(G, n, key_bits, place):
+    """run_segments_ptr with all four arrays in poison: below 2^16 elements (copies and a sort per segment), from 2^16 (segmented
+    passes), 700 001 (ending in LDS); and every count with the inputs, the outputs or both 4 and 12 bytes off a 16-byte boundary, which
+    takes the copies whatever the count.  The inputs' contents are unspecified afterwards; their guards must hold."""
+    segmented_sort(G, G.RadixSort(), n, key_bits, place)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 8. batched sort

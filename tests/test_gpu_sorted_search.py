@@ -4,6 +4,7 @@ both paths.  Expected values are always numpy.searchsorted(enc(hay), enc(needles
 it and behind it, and is itself filled with poison first; the inputs are checked unchanged.  The scheme is that of
 test_gpu_select.py."""
 import ctypes
+import gc
 import os
 import subprocess
 
@@ -498,6 +499,7 @@ def test_prepared_captured_replayed(G):
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         assert ss.last() == (INDEXED, 3, 2)
         verify(*data)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for spread in (2 ** 32, 5000, 3):  # all keys different, twenty copies of every key, three keys

@@ -4,6 +4,7 @@ side) per segment on the keys as the sort encodes them, compared with `==`; a ne
 Every array the call reads or writes sits inside an allocation with poison in front of it and behind it, the outputs are filled with
 poison first, the inputs are checked unchanged and last() is held against the plan.  Offsets are always well-formed here; malformed
 ones are tests/test_search_batch_walk.py's.  The scheme is that of test_gpu_sorted_search.py."""
+import gc
 import os
 import subprocess
 
@@ -408,6 +409,7 @@ def test_captured_from_the_first_call_and_replayed(G):
         fill(contents[0])
         side.synchronize()
         held = torch.cuda.mem_get_info()[0]
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)  # the first calls of a and b
         assert a.last() == (BATCH, 0, 1) and b.last() == (BATCH, 0, 1)

@@ -2,6 +2,7 @@
 numpy.argsort(code(keys), kind="stable")[:k], where code is the sort's key code (complemented for largest): boundaries of the tiles
 and of k, ties at the threshold, the order of floats, both paths at small sizes, the output contract, refusals, capture, determinism,
 indices past 2^31, the operator among the family, and the C++ program."""
+import gc
 import os
 import subprocess
 
@@ -434,6 +435,7 @@ def test_prepared_captured_replayed(G):
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
         verify(data, path)
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         for data, path in contents:

@@ -2,6 +2,7 @@
 array bit for bit against numpy.argsort(code(segment), kind="stable")[:min(k, len)] per segment, where code is the sort's key code
 (complemented for largest); indices local to the segment, rows of stride k, untouched entries still poison.  The class limits, the
 loop threshold and the kernel counts are read from glu_top_k_plan_batch, never written here."""
+import gc
 import os
 import subprocess
 
@@ -340,6 +341,7 @@ def test_capture_replays_on_new_contents_and_twice_gives_the_same_bits(G):
         call(side.cuda_stream)
         side.synchronize()
         assert torch.cuda.mem_get_info()[0] == held, "a prepared call changed the device memory in use"
+        gc.collect()  # (a dead cycle that holds an operator object is finalised here, not inside the capture: destroying one waits for the device)
         with torch.cuda.graph(graph, stream=side):
             call(torch.cuda.current_stream().cuda_stream)
         seen = []
