@@ -17,7 +17,7 @@
 //   glu_reduce_batch.hip      the batched reduce: every segment of an array folded on its own (reduce_batch_kernels.hpp)
 //   glu_scan_batch.hip        the batched scan: every segment of an array scanned on its own (scan_batch_kernels.hpp)
 //   glu_key_runs.hip          key runs: the offsets of the runs of equal keys, for the three batched units (key_runs_kernels.hpp)
-//   glu_select.hip            select: stable stream compaction by a stencil and a comparison (select_kernels.hpp)
+//   glu_select.hip            select: stable stream compaction by a stencil and a comparison (select_kernels.hpp), and its batched form (select_batch_kernels.hpp)
 //   glu_sorted_search.hip     sorted search: lower and upper bounds of many needles in a sorted haystack (sorted_search_kernels.hpp),
 //                             and every segment's needles in its own haystack (sorted_search_batch_kernels.hpp over search_batch_walk.hpp)
 //   glu_merge.hip             merge: two sorted arrays of keys and values into one, stable (merge_kernels.hpp over merge_path.hpp)

@@ -28,6 +28,13 @@ namespace glu
         SelectOperator_GreaterEqual = GLU_SELECT_GE
     };
 
+    /// What out_indices of a batched call holds: the index in the array, or in the element's segment.
+    enum SelectIndex
+    {
+        SelectIndex_Global = GLU_SELECT_INDEX_GLOBAL,
+        SelectIndex_Local = GLU_SELECT_INDEX_LOCAL
+    };
+
     /// The arrays of one Select call (glu_select_run_ptr in glu_hip.h).  All pointers are device pointers but `threshold`.
     struct SelectArrays
     {
@@ -77,6 +84,49 @@ namespace glu
         {
             GLU_CHECK_STATUS(glu_select_run_ptr(m_impl, device_stencil, stencil_type, op, host_threshold, count, device_items, item_bytes,
                                                 device_out_items, device_out_indices, max_out, device_num_selected, stream));
+        }
+
+        /// Scratch for batches of up to `total` elements (about total / 8 bytes): the batched calls then allocate nothing.
+        void prepare_batch(size_t total, size_t num_segments, SelectStencil stencil_type = SelectStencil_Uint)
+        {
+            GLU_CHECK_STATUS(glu_select_prepare_batch(m_impl, total, num_segments, stencil_type));
+        }
+
+        /// The select of `a` over a.count = count * num_partitions elements in segments of `count`: the same compaction, and
+        /// out_offsets[s] = min(a.max_out, the selected elements in front of segment s) for s = 0 .. num_partitions (nullptr skips
+        /// it) -- the offsets of the compacted segments, in the form every batched operator takes.  SelectIndex_Local writes the
+        /// index inside the element's segment.  a.count is not looked at.
+        void select_batch(const SelectArrays& a, size_t count, size_t num_partitions, uint32_t* out_offsets,
+                          SelectIndex index_form = SelectIndex_Global, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_select_run_batch_ptr(m_impl, a.stencil, a.stencil_type, a.op, a.threshold, count, num_partitions, a.items,
+                                                      a.item_bytes, a.out_items, a.out_indices, index_form, a.max_out, out_offsets,
+                                                      a.num_selected, stream));
+        }
+
+        /// The same over the segments [offsets[s], offsets[s + 1]) of device offsets (num_segments + 1 words, what KeyRuns writes),
+        /// a.count being the length of the arrays: only elements from offsets[0] to offsets[num_segments] can be selected.
+        void select_batch_offsets(const SelectArrays& a, const uint32_t* offsets, size_t num_segments, uint32_t* out_offsets,
+                                  SelectIndex index_form = SelectIndex_Global, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_select_run_batch_offsets_ptr(m_impl, a.stencil, a.stencil_type, a.op, a.threshold, a.count, offsets,
+                                                              num_segments, a.items, a.item_bytes, a.out_items, a.out_indices, index_form,
+                                                              a.max_out, out_offsets, a.num_selected, stream));
+        }
+
+        /// What a batched call does (glu_select_plan_batch; host only, no device needed).
+        struct BatchPlan
+        {
+            uint32_t tile = 0, tiles = 0, scan_rounds = 0, kernels = 0;
+            size_t scratch_bytes = 0;
+        };
+        [[nodiscard]] static BatchPlan plan_batch(size_t total, size_t num_segments, SelectStencil stencil_type = SelectStencil_Uint,
+                                                  SelectIndex index_form = SelectIndex_Global)
+        {
+            BatchPlan p;
+            GLU_CHECK_STATUS(glu_select_plan_batch(total, num_segments, stencil_type, index_form, &p.tile, &p.tiles, &p.scan_rounds, &p.kernels,
+                                                   &p.scratch_bytes));
+            return p;
         }
 
         /// Bytes of an item of `data_type` (4, 8, 16 or 32): what item_bytes takes for arrays of Vec4, DVec4 and the like.

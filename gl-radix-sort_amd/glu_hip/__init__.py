@@ -20,6 +20,8 @@ ReduceOperator_Sum, ReduceOperator_Mul, ReduceOperator_Min, ReduceOperator_Max =
 # glu_select_run_ptr: the stencil types (the four scalar data types with their values, and a byte) and the comparisons
 SelectStencil_Float, SelectStencil_Double, SelectStencil_Int, SelectStencil_Uint, SelectStencil_Byte = 0, 1, 2, 3, 12
 SelectOperator_EQ, SelectOperator_NE, SelectOperator_LT, SelectOperator_LE, SelectOperator_GT, SelectOperator_GE = range(6)
+# glu_select_run_batch_ptr: what out_indices holds (the index in the array, or in the element's segment)
+SelectIndex_Global, SelectIndex_Local = 0, 1
 # glu_sorted_search_set_option("PATH", ...) and what glu_sorted_search_plan / glu_sorted_search_last report
 SearchPath_Auto, SearchPath_Direct, SearchPath_Indexed = range(3)
 SearchPath_Batch = 3  # what glu_sorted_search_last reports after a batched call (never an option)
@@ -122,6 +124,10 @@ SYMBOLS = [
     ("glu_select_prepare", _int, [_vp, _sz, _int]),
     ("glu_select_run_ptr", _int, [_vp, _vp, _int, _int, _vp, _sz, _vp, _u32, _vp, _vp, _sz, _vp, _vp]),
     ("glu_select_plan", _int, [_sz, _int, _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_select_prepare_batch", _int, [_vp, _sz, _sz, _int]),
+    ("glu_select_run_batch_ptr", _int, [_vp, _vp, _int, _int, _vp, _sz, _sz, _vp, _u32, _vp, _vp, _int, _sz, _vp, _vp, _vp]),
+    ("glu_select_run_batch_offsets_ptr", _int, [_vp, _vp, _int, _int, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _int, _sz, _vp, _vp, _vp]),
+    ("glu_select_plan_batch", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_sorted_search_create", _int, [_P(_vp)]),
     ("glu_sorted_search_destroy", _int, [_vp]),
     ("glu_sorted_search_prepare", _int, [_vp, _sz, _int]),
@@ -396,6 +402,16 @@ def plan_select(count, stencil_type=SelectStencil_Uint):
     a, b, c = _u32(0), _u32(0), _u32(0)
     check(lib().glu_select_plan(count, stencil_type, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
     return a.value, b.value, c.value
+
+
+def plan_select_batch(total, num_segments, stencil_type=SelectStencil_Uint, index_form=SelectIndex_Global):
+    """(tile, tiles, scan_rounds, kernels, scratch_bytes) of a batched select over `total` elements in `num_segments` segments
+    (glu_select_plan_batch; host only): tile and tiles as plan_select's, the rounds of the scan of tiles + 1 counts, the kernels of a
+    call with all three outputs, the bytes prepare_batch reserves."""
+    a, b, c, d, e = _u32(0), _u32(0), _u32(0), _u32(0), _sz(0)
+    check(lib().glu_select_plan_batch(total, num_segments, stencil_type, index_form, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                      ctypes.byref(d), ctypes.byref(e)))
+    return a.value, b.value, c.value, d.value, e.value
 
 
 def plan_sorted_search(hay_count, needle_count, key_type="uint32", top_entries=0):
@@ -751,9 +767,17 @@ class Select(_Handle):
         out_indices[r] = the index of the r-th selected element, out_items[r] = its item (either may be None), for r below
         min(selected, max_out); *num_selected = the number selected, also beyond max_out.  All pointers are device pointers; the
         stencil and the items are only read (glu_select_run_ptr)."""
+        value = self._threshold(threshold, stencil_type)
+        check(lib().glu_select_run_ptr(self._h, _vp(stencil_ptr), stencil_type, op, ctypes.byref(value) if value is not None else None, count,
+                                       _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr), max_out, _vp(num_selected_ptr),
+                                       _vp(stream)))
+
+    @classmethod
+    def _threshold(cls, threshold, stencil_type):
+        """`threshold` packed into the stencil's type (None: the call's NULL, zero)."""
         value = None
-        if threshold is not None and stencil_type in self._THRESHOLD_TYPES:
-            ctype = self._THRESHOLD_TYPES[stencil_type]
+        if threshold is not None and stencil_type in cls._THRESHOLD_TYPES:
+            ctype = cls._THRESHOLD_TYPES[stencil_type]
             if ctype not in (ctypes.c_float, ctypes.c_double):
                 bits = 8 * ctypes.sizeof(ctype)
                 lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if ctype is ctypes.c_int32 else (0, (1 << bits) - 1)
@@ -761,9 +785,34 @@ class Select(_Handle):
                     raise GluError(GLU_ERROR_INVALID_ARGUMENT, "threshold %r is no value of the stencil's type" % (threshold,))
                 threshold = int(threshold)
             value = ctype(threshold)
-        check(lib().glu_select_run_ptr(self._h, _vp(stencil_ptr), stencil_type, op, ctypes.byref(value) if value is not None else None, count,
-                                       _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr), max_out, _vp(num_selected_ptr),
-                                       _vp(stream)))
+        return value
+
+    def prepare_batch(self, total, num_segments, stencil_type=SelectStencil_Uint):
+        """Scratch for batches of up to `total` elements: after it the batched calls allocate nothing (capturable)
+        (glu_select_prepare_batch)."""
+        check(lib().glu_select_prepare_batch(self._h, total, num_segments, stencil_type))
+
+    def run_batch_ptr(self, stencil_ptr, count, num_partitions, max_out, num_selected_ptr, out_indices_ptr=None, items_ptr=None,
+                      out_items_ptr=None, item_bytes=4, out_offsets_ptr=None, index_form=SelectIndex_Global,
+                      stencil_type=SelectStencil_Uint, op=SelectOperator_NE, threshold=None, stream=None):
+        """run_ptr over `num_partitions` segments of `count` elements each: the same compaction, out_offsets[0 .. num_partitions] = the
+        offsets of the compacted segments (clamped to max_out), and with SelectIndex_Local the indices inside the element's segment
+        (glu_select_run_batch_ptr)."""
+        value = self._threshold(threshold, stencil_type)
+        check(lib().glu_select_run_batch_ptr(self._h, _vp(stencil_ptr), stencil_type, op, ctypes.byref(value) if value is not None else None,
+                                             count, num_partitions, _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr),
+                                             index_form, max_out, _vp(out_offsets_ptr), _vp(num_selected_ptr), _vp(stream)))
+
+    def run_batch_offsets_ptr(self, stencil_ptr, total, offsets_ptr, num_segments, max_out, num_selected_ptr, out_indices_ptr=None,
+                              items_ptr=None, out_items_ptr=None, item_bytes=4, out_offsets_ptr=None, index_form=SelectIndex_Global,
+                              stencil_type=SelectStencil_Uint, op=SelectOperator_NE, threshold=None, stream=None):
+        """The same over the segments [offsets[s], offsets[s + 1]) of device offsets (num_segments + 1 words, what KeyRuns writes):
+        only the elements from offsets[0] to offsets[num_segments] can be selected (glu_select_run_batch_offsets_ptr)."""
+        value = self._threshold(threshold, stencil_type)
+        check(lib().glu_select_run_batch_offsets_ptr(self._h, _vp(stencil_ptr), stencil_type, op,
+                                                     ctypes.byref(value) if value is not None else None, total, _vp(offsets_ptr), num_segments,
+                                                     _vp(items_ptr), item_bytes, _vp(out_items_ptr), _vp(out_indices_ptr), index_form, max_out,
+                                                     _vp(out_offsets_ptr), _vp(num_selected_ptr), _vp(stream)))
 
 
 class SortedSearch(_Handle):

@@ -668,6 +668,70 @@ GLU_API glu_status glu_select_run_ptr(glu_select select, const void* stencil, in
  * rounds the one workgroup that scans the tile counts makes (4096 counts each).  Any pointer may be NULL. */
 GLU_API glu_status glu_select_plan(size_t count, int stencil_type, uint32_t* tile, uint32_t* tiles, uint32_t* scan_rounds);
 
+/* ---- batched select (not in the reference): the select above over the segments of the batched family, in one launch sequence.
+ * It compacts the selected elements exactly as glu_select_run_ptr does, writes the OFFSETS OF THE COMPACTED SEGMENTS in the form
+ * every batched operator takes, and can write indices local to the segment: filtering ragged data while keeping the groups --
+ * the samples of each group above a threshold, each row's non-zeros -- with the rows of a batched reduce, histogram or top-k made
+ * before the filter still lining up, because an emptied segment stays an empty segment.
+ *   - The segments are equal partitions (`count` elements each, `num_partitions` of them: total = count * num_partitions,
+ *     b_s = s * count), or device `offsets` (uint32, num_segments + 1 entries, what glu_key_runs_run_ptr writes):
+ *     b_s = min(offsets[s], total) for s = 0 .. num_segments.  THE CONTRACT IS TOTAL: it defines a result for malformed offsets.
+ *   - Element i is SELECTED iff b_0 <= i < b_num_segments and stencil[i] OP threshold.  Elements outside that range are never
+ *     selected (expand's rule).  The stencil types, the six comparisons, the host threshold passed by value, the item widths and
+ *     the alignment rules are those of glu_select_run_ptr.
+ *   - S = the number selected, i_0 < i_1 < ... their indices.  out_items[r] = items[i_r] for r < min(S, max_out); entries at or
+ *     behind that are not touched.  *num_selected = S, the true number: overflow shows as *num_selected > max_out.
+ *   - out_indices, index_form GLU_SELECT_INDEX_GLOBAL: out_indices[r] = i_r.  GLU_SELECT_INDEX_LOCAL: out_indices[r] = i_r - b_s
+ *     with s the last segment whose b_s <= i_r (numpy.searchsorted(offsets, i, "right") - 1, what expand and the batched top-k
+ *     mean by a segment's element).
+ *   - out_offsets[s] = min(max_out, the number of selected i < b_s) for EVERY s = 0 .. num_segments.  With non-decreasing offsets
+ *     out_offsets[0] = 0 and segment s of the compacted arrays is [out_offsets[s], out_offsets[s + 1]).  The offsets are clamped
+ *     to max_out: they always describe what was written, and a following batched call stays in bounds.
+ *   - Offsets that decrease or lie beyond total: the definitions above still hold for out_offsets, the items, the GLOBAL indices
+ *     and *num_selected; LOCAL indices are then unspecified; nothing outside the arrays is read or written in any case.
+ *   - Each of the three outputs is optional: out_offsets may be NULL, out_indices may be NULL, items and out_items are both NULL
+ *     or both given.  With only out_offsets the call counts per segment.  num_segments == 0 writes *num_selected = 0 and nothing
+ *     else.
+ *   - Limits: total < 2^32; num_segments <= 2^24; max_out < 2^32; offsets and out_offsets aligned to 4 bytes.
+ *   - GLU_ERROR_INVALID_ARGUMENT, with a message that names the argument and nothing written, for everything the single call
+ *     refuses; NULL or misaligned offsets; a misaligned out_offsets; an index_form outside 0 .. 1; out_offsets overlapping an
+ *     input or another output; offsets overlapping an output.
+ *   - The call only enqueues on `stream`: no host synchronisation, no read-back, no atomics, no look-back, nothing in arrival
+ *     order, and no device allocation once glu_select_prepare_batch covered the sizes.  At most four kernels, whose grids follow
+ *     from total, num_segments and the address of the stencil, never from the data: the single call's count, which also stores one
+ *     flag bit per element and the wave sums of every tile; the count scan; one thread per boundary, which reads a scanned count,
+ *     a wave sum and one wave's flag words (two or three cache lines per boundary whatever the data hold: 2^24 empty segments at
+ *     one position are 2^24 threads, not one workgroup's loop); the single call's write, which takes its flags from the stored
+ *     bits -- the batched call reads the stencil ONCE.  A captured call replays on other contents and on other offsets of the
+ *     same shape.  THE SAME INPUT GIVES THE SAME BITS EVERY TIME. */
+typedef enum glu_select_index
+{
+    GLU_SELECT_INDEX_GLOBAL = 0,
+    GLU_SELECT_INDEX_LOCAL = 1
+} glu_select_index;
+/* Grow-only scratch so that the two calls below allocate nothing (and can be captured) for up to `total` (< 2^32) elements of a
+ * stencil of `stencil_type`, at any number of segments: per tile of the stencil (one more than glu_select_plan's tiles) 4 bytes
+ * of count, 16 bytes of wave sums and tile / 8 bytes of flags -- about total / 8 bytes, the figure glu_select_plan_batch
+ * returns.  It is separate from the single call's scratch. */
+GLU_API glu_status glu_select_prepare_batch(glu_select select, size_t total, size_t num_segments, int stencil_type);
+/* equal partitions; everything but threshold on the DEVICE */
+GLU_API glu_status glu_select_run_batch_ptr(glu_select select, const void* stencil, int stencil_type, int op, const void* threshold,
+                                            size_t count, size_t num_partitions, const void* items, uint32_t item_bytes,
+                                            void* out_items, uint32_t* out_indices, int index_form, size_t max_out,
+                                            uint32_t* out_offsets, uint32_t* num_selected, void* stream);
+/* device offsets */
+GLU_API glu_status glu_select_run_batch_offsets_ptr(glu_select select, const void* stencil, int stencil_type, int op,
+                                                    const void* threshold, size_t total, const uint32_t* offsets, size_t num_segments,
+                                                    const void* items, uint32_t item_bytes, void* out_items, uint32_t* out_indices,
+                                                    int index_form, size_t max_out, uint32_t* out_offsets, uint32_t* num_selected,
+                                                    void* stream);
+/* Host only, pure, no device: tile and tiles as glu_select_plan's for `total` elements; scan_rounds = the rounds of the count scan
+ * over tiles + 1 counts (the last one becomes the total); kernels = those of a call with all three outputs (4; the offsets and the
+ * write kernel drop out with their outputs, and the form changes none; 0 where total or num_segments is 0: the call only clears);
+ * scratch_bytes = what glu_select_prepare_batch reserves (0 where total is 0).  Any pointer may be NULL. */
+GLU_API glu_status glu_select_plan_batch(size_t total, size_t num_segments, int stencil_type, int index_form, uint32_t* tile,
+                                         uint32_t* tiles, uint32_t* scan_rounds, uint32_t* kernels, size_t* scratch_bytes);
+
 /* ---- sorted search (not in the reference): the lower and the upper bound of many needles in a sorted haystack, what
  * numpy.searchsorted is, on the device and on the caller's stream.  A join against the unique keys of key runs, a membership
  * test, the bin index of every sample over arbitrary sorted bin edges (the COUNTS per bin are glu_histogram_run_edges_ptr), the
@@ -1132,7 +1196,7 @@ GLU_API glu_status glu_histogram_read_batch(glu_histogram histogram, uint32_t* w
  *     overlapping offsets, items or another output.  A refused call writes nothing.
  *   - OUT OF SCOPE: a counts-form entry point (the recipe above); items wider than 32 bytes; a gather by an arbitrary permutation (that is
  *     glu_gather_run_ptr);
- *     a segmented select that rewrites offsets; 64-bit offsets. */
+ *     64-bit offsets.  (A segmented select that rewrites offsets is glu_select_run_batch_offsets_ptr.) */
 typedef struct glu_expand_s* glu_expand;
 /* Not in the reference. */
 GLU_API glu_status glu_expand_create(glu_expand* out);
