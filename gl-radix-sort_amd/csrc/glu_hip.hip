@@ -34,6 +34,13 @@ glu_status glu_hip::host::sort_prepare(glu_radix_sort_s* s, size_t count, size_t
     const bool grows = s->keys.size < count * key_size || (with_vals && s->vals.size < count * sizeof(uint32_t));
     if (grows && !s->tuning) // the arrays the last placement search chose (if any) are about to be replaced
         s->tuned_candidates = 0, s->tuned_ms = s->tuned_worst_ms = 0.0, s->tuned_spacer_mib = 0;
+    // The narrow hand-off's side array of 2-byte keys: for the sorts that can take it -- 4-byte keys with values, of a size at which the
+    // attempt to end in LDS is made (the same conditions as the attempt's tables below and in sort_bits).  In front of the placement
+    // search, whose trial sorts then run as the object's sorts will.
+    static_assert(256u * finish_geometry_capacity(kFinishGeometries) < kPlanMinCount, "PassPlan::narrow: a planned sort whose runs all fit a tile has both of its top-bit scatters move data");
+    if (key_size == 4 && with_vals && s->narrow_handoff && s->lds_finish && s->pairs && !s->no_plan && !s->no_lines && !s->force_small &&
+        count >= kPlanMinCount && count >= (s->finish_min ? s->finish_min : finish_min_count(key_size)) && finish_geometry_for(count) != 0)
+        GLU_TRY(s->narrow_keys.reserve(count * sizeof(uint16_t)));
     if (may_place && with_vals && s->tune_scratch && !s->tuning && count * key_size >= kTuneMinKeyBytes && grows)
         GLU_TRY(tune_scratch_placement(s, count, key_size));
     GLU_TRY(s->keys.reserve(count * key_size));
@@ -61,7 +68,7 @@ glu_status glu_hip::host::sort_prepare(glu_radix_sort_s* s, size_t count, size_t
             GLU_TRY(s->finish_lengths.reserve((size_t) kFinishRuns * sizeof(uint32_t)));
             GLU_TRY(s->finish_starts.reserve(((size_t) kFinishRuns + 1) * sizeof(uint32_t)));
             GLU_TRY(s->finish_crowded.reserve(crowded_list_words(kFinishRuns) * sizeof(uint32_t)));
-            GLU_TRY(s->finish_outcomes.reserve(256 * sizeof(uint32_t)));
+            GLU_TRY(s->finish_outcomes.reserve(512 * sizeof(uint32_t))); // (per attempt of a window: outcome and tile; the hand-off)
             GLU_TRY(s->pair_wide.reserve((size_t) nb * kPairWideStride * sizeof(uint32_t)));
             {
                 // runs longer than the in-LDS pass's tile are sorted by segmented passes (radix_finish_long_runs_kernel)
@@ -147,6 +154,7 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
     s->last_planned = false; // (what glu_radix_sort_read_plan / read_finish report is about THIS sort: step 4)
     s->last_finish_attempted = false;
     s->last_finish_long_ok = false;
+    s->last_narrow_offered = false;
 
     if (count <= single_block_limit<KeyT>() && !s->no_single_block)
     {
@@ -200,6 +208,11 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
     // (every key type since round 6; the passes cover 16 low bits of 4-byte keys, 48 of 8-byte keys)
     const bool finish_long_ok = finish_kpt && s->long_runs && s->long_image.ptr && finish_top_bit >= 16 &&
                                 finish_top_bit - 16u <= (sizeof(KeyT) == 4 ? 16u : 48u);
+    // the narrow hand-off (PassPlan::narrow): untyped 4-byte keys with values, on an object whose prepare reserved the side array
+    uint16_t* const narrow_keys = finish_kpt && sizeof(KeyT) == 4 && vals && key_xf == KEY_XF_NONE && s->narrow_handoff &&
+                                          s->narrow_keys.size >= count * sizeof(uint16_t)
+                                      ? (uint16_t*) s->narrow_keys.ptr
+                                      : nullptr;
     const uint32_t finish_last = std::min<uint32_t>(finish_kpt + 2, kFinishGeometries); // the larger tiles enqueued behind it
     // the one that gets a workgroup per run: what this object's last sort took if that is among them, else the uniform-keys one
     const uint32_t finish_expected =
@@ -217,6 +230,7 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
     s->last_planned = planned;
     s->last_finish_attempted = finish_kpt != 0;
     s->last_finish_long_ok = finish_long_ok;
+    s->last_narrow_offered = narrow_keys != nullptr && passes[1].pair_role == 2;
     s->last_device_top = finish_kpt && device_top;
     s->last_finish_top = finish_kpt ? finish_top_bit : 0u;
     s->last_finish_capacity = finish_kpt ? finish_geometry_capacity(finish_last) : 0u;
@@ -228,8 +242,8 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
     {
         // per sort: no follower counts for itself yet, nothing is known about the key bits
         PassPlan* plan = (PassPlan*) s->plan.ptr;
-        static_assert(offsetof(PassPlan, sample_done) + sizeof(plan->sample_done) <= sizeof(PassPlan) && offsetof(PassPlan, sample_done) + 64 > sizeof(PassPlan),
-                      "sample_done is the last member of the zeroed tail of the plan");
+        static_assert(offsetof(PassPlan, narrow) + sizeof(plan->narrow) <= sizeof(PassPlan) && offsetof(PassPlan, narrow) + 64 > sizeof(PassPlan),
+                      "narrow is the last member of the zeroed tail of the plan");
         static_assert(offsetof(PassPlan, pair_fallback) % 64 == 0 && sizeof(PassPlan) % 64 == 0, "one aligned fill");
         HIP_TRY(hipMemsetAsync(plan->pair_fallback, 0, sizeof(PassPlan) - offsetof(PassPlan, pair_fallback), stream));
         if (finish_kpt && device_top)
@@ -295,6 +309,7 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
                 pa.fork_side = fork;
             }
             pa.unitsum_side = fork && pass == 1 && pa.pair_role == 2 && bits == 8;
+            if (finish_kpt && pass < 2 && s->last_narrow_offered) pa.narrow_keys = narrow_keys;
             GLU_TRY(dispatch_pass<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, shift, bits, nullptr,
                                         fork && pa.behind_attempt ? s->side : stream, xform, pa));
             if (finish_kpt && pass == 1)
@@ -311,7 +326,8 @@ glu_status glu_hip::host::sort_bits(glu_radix_sort_s* s, KeyT* keys, uint32_t* v
                 const auto finish = vals ? (key_xf != KEY_XF_NONE ? launch_finish<KeyT, true, true> : launch_finish<KeyT, true, false>)
                                          : (key_xf != KEY_XF_NONE ? launch_finish<KeyT, false, true> : launch_finish<KeyT, false, false>);
                 GLU_TRY(finish(kbuf[0], vbuf[0], kbuf[1], vbuf[1], (const uint32_t*) s->finish_starts.ptr, finish_kpt, finish_last, finish_expected,
-                               finish_top_bit - 16u, pa.plan, 2u, key_xf, stream, s->finish_rank_bits, (uint32_t*) s->finish_crowded.ptr, finish_marks));
+                               finish_top_bit - 16u, pa.plan, 2u, key_xf, stream, s->finish_rank_bits, (uint32_t*) s->finish_crowded.ptr, finish_marks,
+                               s->last_narrow_offered ? (const uint16_t*) narrow_keys : (const uint16_t*) nullptr));
                 if (finish_long_ok && !fork)
                     GLU_TRY(launch_long_run_passes_any<KeyT>(s, kbuf[0], vbuf[0], kbuf[1], vbuf[1], count, key_xf, stream));
             }
@@ -393,6 +409,7 @@ const SortOption kSortOptions[] = {
     GLU_OPT("SORT_LDS_FINISH", s->lds_finish = v != 0),
     GLU_OPT("SEG_LDS_FINISH", s->seg_finish = v != 0),
     GLU_OPT("SORT_LONG_RUNS", s->long_runs = v != 0),
+    GLU_OPT("SORT_NARROW_HANDOFF", s->narrow_handoff = v != 0), // (decides an allocation: takes effect with the next prepare)
     GLU_OPT("SORT_DEVICE_TOP", s->device_top = v != 0),
     GLU_OPT("SORT_FORK", s->fork_behind = v != 0),
     GLU_OPT("SEG_SPLIT_MAX", s->seg_split_max = (uint32_t) std::min<long long>(std::max<long long>(v, 0), 3)),
@@ -630,7 +647,7 @@ glu_status glu_radix_sort_set_profiling(glu_radix_sort sort, int enable)
     GLU_TRY(enter());
     GLU_TRY(check_not_null(sort, "sort"));
     sort->profiling = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
-    if (!enable) sort->events_used = 0, sort->slots.clear(), sort->pass_kinds.clear(), sort->pass_seqs.clear();
+    if (!enable) sort->clear_marks();
     return GLU_OK;
 }
 
@@ -702,6 +719,19 @@ glu_status glu_radix_sort_read_finish(glu_radix_sort sort, uint32_t* attempted, 
     return GLU_OK;
 }
 
+// Which hand-off between the second top-bit scatter and the in-LDS pass the last sort took: narrow = 1: 2-byte keys in the object's
+// side array (PassPlan::narrow); 0: whole keys in the key array, or the sort did not end in LDS.
+glu_status glu_radix_sort_read_handoff(glu_radix_sort sort, uint32_t* narrow)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(sort, "sort"));
+    const bool offered = last_sort_tried(sort) && sort->last_narrow_offered;
+    PassPlan host;
+    GLU_TRY(read_device_plan(sort, offered, host));
+    store(narrow, offered && host.finish && host.narrow ? 1u : 0u);
+    return GLU_OK;
+}
+
 // Sums the recorded intervals.  Sorts that tried to end in LDS (radix_lds_finish.hpp) enqueue two sequences of passes, one of
 // which returns at once; which one is read from the plan of the LAST sort and assumed for every sort since the previous
 // read.  Booked are the passes that did the work: accepted -- the two top-bit passes (count / scan / scatter) and the in-LDS
@@ -719,9 +749,10 @@ glu_status glu_radix_sort_read_profile_finish(glu_radix_sort sort, double* count
     GLU_TRY(read_device_plan(sort, last_sort_tried(sort), host));
     const bool last_accepted = host.finish != 0;
     // the outcome of every attempt of the window, by attempt number (a window of more than 256 sorts: the older ones by the last)
-    std::vector<uint32_t> ring(256, 0u);
+    // (words 256 .. 511: attempt number << 1 | the sort took the narrow hand-off)
+    std::vector<uint32_t> ring(512, 0u);
     const bool have_ring = sort->finish_outcomes.ptr != nullptr;
-    if (have_ring) HIP_TRY(hipMemcpy(ring.data(), sort->finish_outcomes.ptr, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (have_ring) HIP_TRY(hipMemcpy(ring.data(), sort->finish_outcomes.ptr, 512 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     bool seg_tried = false;
     uint32_t seg_longest = 0;
     GLU_TRY(read_seg_gate(sort, seg_tried, seg_longest));
@@ -741,6 +772,16 @@ glu_status glu_radix_sort_read_profile_finish(glu_radix_sort sort, double* count
         // (light profiling records no events around the sequence the host expects not to run: such a pass is not a live pass with
         // zero time, whatever the device then decided)
         const bool timed = sort->slots[p * 4 + 2] && sort->slots[p * 4 + 3];
+        // (the second top-bit scatter in two forms: the interval of the form that moved the data, by this sort's hand-off)
+        if (timed && p < sort->between_forms.size() && sort->between_forms[p])
+        {
+            bool narrow = host.narrow != 0u;
+            if (seq && have_ring && (ring[256u + (seq & 255u)] >> 1) == seq) narrow = (ring[256u + (seq & 255u)] & 1u) != 0u;
+            if (narrow)
+                HIP_TRY(hipEventElapsedTime(&ms[2], sort->between_forms[p], sort->slots[p * 4 + 3]));
+            else
+                HIP_TRY(hipEventElapsedTime(&ms[2], sort->slots[p * 4 + 2], sort->between_forms[p]));
+        }
         if (kind == 2)
         {
             if (accepted || seg_accepted) fin += ms[2], fin_n++;
@@ -762,10 +803,7 @@ glu_status glu_radix_sort_read_profile_finish(glu_radix_sort sort, double* count
         for (int k = 0; k < 3; k++) acc[k] += ms[k];
         live++;
     }
-    sort->events_used = 0;
-    sort->slots.clear();
-    sort->pass_kinds.clear();
-    sort->pass_seqs.clear();
+    sort->clear_marks();
     store(count_ms, acc[0]);
     store(scan_ms, acc[1]);
     store(scatter_ms, acc[2]);

@@ -66,7 +66,7 @@ template<typename KeyT, bool VALS, bool XF>
 glu_status launch_finish(KeyT* keys_a, uint32_t* vals_a, KeyT* keys_b, uint32_t* vals_b, const uint32_t* starts,
                          uint32_t geo_first, uint32_t geo_last, uint32_t geo_expected, uint32_t low_bits, const PassPlan* plan,
                          uint32_t pass, uint32_t key_xf, hipStream_t stream, uint32_t rank_bits, uint32_t* crowded,
-                         FinishMarks marks)
+                         FinishMarks marks, const uint16_t* narrow_keys)
 {
     // (marks: the two profile marks of the in-LDS pass go around the launch of the EXPECTED tile, the one that does the work in
     // a timed loop -- not around the launches beside it that return at once)
@@ -92,7 +92,7 @@ glu_status launch_finish(KeyT* keys_a, uint32_t* vals_a, KeyT* keys_b, uint32_t*
         if (GEO_ == geo_expected) marks(stream);                                                                                    \
         hipLaunchKernelGGL(kern, dim3(GEO_ == geo_expected ? nruns : std::min(nruns, 8192u)), dim3(THREADS_), sizeof(Smem),       \
                            stream, keys_a, vals_a, keys_b, vals_b, starts, low_bits, plan, pass, (uint32_t) GEO_, key_xf, nruns,  \
-                           crowded);                                                                                              \
+                           crowded, narrow_keys);                                                                                 \
         if (GEO_ == geo_expected) marks(stream);                                                                                    \
         HIP_TRY(hipGetLastError());                                                                                               \
     }
@@ -160,7 +160,7 @@ glu_status launch_finish(KeyT* keys_a, uint32_t* vals_a, KeyT* keys_b, uint32_t*
 #define GLU_LAUNCH_FINISH_DEFINE(K_, V_, X_)                                                                                      \
     template glu_status launch_finish<K_, V_, X_>(K_*, uint32_t*, K_*, uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,  \
                                                   uint32_t, const PassPlan*, uint32_t, uint32_t, hipStream_t, uint32_t,          \
-                                                  uint32_t*, FinishMarks);
+                                                  uint32_t*, FinishMarks, const uint16_t*);
 GLU_LAUNCH_FINISH_INSTANCES(GLU_LAUNCH_FINISH_DEFINE)
 #undef GLU_LAUNCH_FINISH_DEFINE
 } // namespace host

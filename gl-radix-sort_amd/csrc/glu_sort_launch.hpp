@@ -54,19 +54,19 @@ glu_status launch_seg_finish(const uint32_t* src_k, const uint32_t* src_v, uint3
 // expected to take gets a workgroup per run, the others 8192 workgroups that loop --, and behind them round 5's ballot-ranked
 // kernel for the runs the bucket kernel listed as crowded (or for all of them: PassPlan::finish_rounds), two launches split by the
 // runs' length: the expected tile for the runs that fit it, the largest enqueued tile for the longer ones.  They return at once
-// when the lists are empty.
+// when the lists are empty.  narrow_keys: the side array of 2-byte keys of a sort that may take the narrow hand-off (PassPlan::narrow), or NULL.
 template<typename KeyT, bool VALS, bool XF>
 glu_status launch_finish(KeyT* keys_a, uint32_t* vals_a, KeyT* keys_b, uint32_t* vals_b, const uint32_t* starts,
                          uint32_t geo_first, uint32_t geo_last, uint32_t geo_expected, uint32_t low_bits, const PassPlan* plan,
                          uint32_t pass, uint32_t key_xf, hipStream_t stream, uint32_t rank_bits, uint32_t* crowded,
-                         FinishMarks marks);
+                         FinishMarks marks, const uint16_t* narrow_keys);
 #define GLU_LAUNCH_FINISH_INSTANCES(X_)                                                                                           \
     X_(uint32_t, true, false) X_(uint32_t, true, true) X_(uint32_t, false, false) X_(uint32_t, false, true)                       \
     X_(uint64_t, true, false) X_(uint64_t, true, true) X_(uint64_t, false, false) X_(uint64_t, false, true)
 #define GLU_LAUNCH_FINISH_EXTERN(K_, V_, X_)                                                                                      \
     extern template glu_status launch_finish<K_, V_, X_>(K_*, uint32_t*, K_*, uint32_t*, const uint32_t*, uint32_t, uint32_t,     \
                                                          uint32_t, uint32_t, const PassPlan*, uint32_t, uint32_t, hipStream_t,   \
-                                                         uint32_t, uint32_t*, FinishMarks);
+                                                         uint32_t, uint32_t*, FinishMarks, const uint16_t*);
 GLU_LAUNCH_FINISH_INSTANCES(GLU_LAUNCH_FINISH_EXTERN)
 #undef GLU_LAUNCH_FINISH_EXTERN
 } // namespace host

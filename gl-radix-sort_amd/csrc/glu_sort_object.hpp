@@ -172,6 +172,12 @@ struct glu_radix_sort_s
     Scratch finish_lengths;       // [65536] run lengths,
     Scratch finish_starts;        // [65537] run starts
     Scratch finish_crowded;       // the runs the bucket kernel of the in-LDS pass leaves to the ballot rounds (crowded_list_words)
+    // The narrow hand-off: uint16[n], the low 16 bits of every key between the second top-bit scatter and the
+    // in-LDS pass of a sort of untyped 4-byte keys with values whose device-side plan says so (PassPlan::narrow).  n x 2 bytes, reserved
+    // by sort_prepare for such sorts of a size at which the attempt to end in LDS is made.
+    Scratch narrow_keys;
+    bool narrow_handoff = true;   // GLU_HIP_SORT_NARROW_HANDOFF=0: whole keys in the key array, as before, and no side array (looked at by sort_prepare: set it before that)
+    bool last_narrow_offered = false; // the last sort enqueued both forms of its second top-bit scatter (glu_radix_sort_read_handoff)
     // (round 6) A sort that tries to end in LDS enqueues two sequences of which the device runs one; the launches of the other
     // return at once, 4.5-5.7 us each -- 22 of them were 105 us behind every accepted attempt (profiles/r05/last_sort_kernels_2p28.txt).
     // They now go to a stream of the object's own that forks off the caller's queue behind the plan kernel and joins it in front
@@ -250,18 +256,28 @@ struct glu_radix_sort_s
     void mark(hipStream_t stream, bool around_data_kernel = false)
     {
         if (!profiling) return;
-        if (slots.size() % 4 == 0) pass_kinds.push_back(cur_kind), pass_seqs.push_back(cur_seq);
+        if (slots.size() % 4 == 0) pass_kinds.push_back(cur_kind), pass_seqs.push_back(cur_seq), between_forms.push_back(nullptr);
         hipEvent_t e = nullptr;
         if (profiling == 1 || (around_data_kernel && !cur_behind))
             if ((e = next_event()) != nullptr) (void) hipEventRecord(e, stream);
         slots.push_back(e);
     }
+    // The second top-bit scatter of a sort that may take the narrow hand-off is two launches between the pass's last two marks, of which
+    // one returns at once: an event between them, per pass (nullptr: one launch), tells glu_radix_sort_read_profile the interval of each.
+    std::vector<hipEvent_t> between_forms;
+    void mark_between_forms(hipStream_t stream)
+    {
+        if (!profiling || between_forms.empty() || (profiling != 1 && cur_behind)) return;
+        hipEvent_t e = next_event();
+        if (e && hipEventRecord(e, stream) == hipSuccess) between_forms.back() = e;
+    }
+    void clear_marks() { events_used = 0, slots.clear(), pass_kinds.clear(), pass_seqs.clear(), between_forms.clear(); }
     // Every Scratch member, once: what release() frees and glu_radix_sort_scratch_size sums.  A new one is added here and nowhere else.
     template<typename F>
     void for_each_scratch(F&& f)
     {
         for (Scratch* sc : {&keys, &vals, &table, &plan, &pair_t2, &pair_table, &pair_ranges, &pair_sub, &pair_wide, &seg_desc, &seg_zero, &batch_lists,
-                            &long_image, &long_hdr, &long_bits, &seg_gate, &finish_lengths, &finish_starts, &finish_crowded, &finish_outcomes})
+                            &long_image, &long_hdr, &long_bits, &seg_gate, &finish_lengths, &finish_starts, &finish_crowded, &finish_outcomes, &narrow_keys})
             f(*sc);
     }
     // everything the object owns (create_object / destroy_object of glu_host.hpp; the caller has drained the device)
@@ -329,6 +345,9 @@ struct PlanArgs
     bool finish_long_ok = false; // runs longer than the tile go to segmented passes (sort_bits enqueues them behind the in-LDS pass)
     bool fork_side = false;      // behind the plan kernel of this pass the object's side stream forks off (glu_radix_sort_s::side)
     bool unitsum_side = false;   // this follower's unit sums run on the side stream, under its leader's scatter
+    // the narrow hand-off: on pass 0, tells the plan kernel that the sort may take it; on pass 1, the second top-bit scatter is enqueued in
+    // both forms (radix_scatter_lines_kernel, NARROW) and the device runs one
+    uint16_t* narrow_keys = nullptr;
 };
 
 constexpr size_t kSmallResidentPerCU = 4; // workgroups of the small pair geometry (512 x 8) that share a CU (measured: the step in sort time sits at 256 x 4 x 4096 pairs)

@@ -81,6 +81,16 @@ glu_status launch_pass(glu_radix_sort_s* s, const KeyT* src_k, const uint32_t* s
     return GLU_OK;
 }
 
+// The instantiation of the line scatter that a pass of the library runs, in one place.  NT: non-temporal line stores.  BEHIND: the same
+// kernel under another name for the ordinary passes enqueued behind an attempt to end in LDS.  NARROW: 1 / 2 = the whole-key / the narrow
+// form of the second top-bit scatter of a sort that may take the narrow hand-off (radix_scatter_lines.hpp).
+template<typename KeyT, int BITS, bool XF, bool VALS, bool NT, bool BEHIND = false, int NARROW = 0>
+constexpr auto lines_scatter_kernel()
+{
+    using G = LinesGeometry<KeyT, BITS, VALS>;
+    return radix_scatter_lines_kernel<KeyT, BITS, G::THREADS, G::KPT, XF, VALS, 0, false, (G::KPT + 2) / 3, true, NT, 0, false, false, BEHIND, NARROW>;
+}
+
 // Large inputs of 4-byte keys in 16-byte aligned arrays: the same three launches with the 128-byte-line scatter kernel
 // (its own tile size, shared by the count kernel: both cut the input with block_tile_range).
 template<typename KeyT, int BITS, bool XF, bool VALS>
@@ -108,16 +118,15 @@ glu_status launch_pass_lines(glu_radix_sort_s* s, const KeyT* src_k, const uint3
     // the line stores are non-temporal: what a pass writes is next read by the count kernel of the following pass, a
     // once-through stream that runs at full speed only if the lines are not sitting dirty in L2 / Infinity Cache
     // (count behind a plain-store scatter 0.206 ms, behind a non-temporal one 0.160 ms; the scatter itself is level)
-    constexpr int RS = (G::KPT + 2) / 3;
-    auto scatter_nt = radix_scatter_lines_kernel<KeyT, BITS, G::THREADS, G::KPT, XF, VALS, 0, false, RS, true, true>;
-    auto scatter_plain = radix_scatter_lines_kernel<KeyT, BITS, G::THREADS, G::KPT, XF, VALS, 0, false, RS, true, false>;
+    auto scatter_nt = lines_scatter_kernel<KeyT, BITS, XF, VALS, true>();
+    auto scatter_plain = lines_scatter_kernel<KeyT, BITS, XF, VALS, false>();
     // the same kernel under another name for the ordinary passes enqueued behind an attempt to end in LDS: they return at
     // once when the attempt was accepted, and a kernel trace's per-name statistics of the scatter stay those of launches
     // that moved data
     auto scatter_behind = scatter_nt;
     constexpr bool kHasBehind = BITS == 8 && !XF; // (the sorts that make such attempts)
     if constexpr (kHasBehind)
-        scatter_behind = radix_scatter_lines_kernel<KeyT, BITS, G::THREADS, G::KPT, XF, VALS, 0, false, RS, true, true, 0, false, false, true>;
+        scatter_behind = lines_scatter_kernel<KeyT, BITS, XF, VALS, true, true>();
     static std::once_flag lds_opt_in; // per instantiation: allow > 64 KiB of dynamic LDS
     static hipError_t lds_opt_in_result = hipSuccess;
     std::call_once(lds_opt_in, [&] {
@@ -238,7 +247,7 @@ glu_status launch_pass_lines(glu_radix_sort_s* s, const KeyT* src_k, const uint3
                            (uint32_t*) s->finish_starts.ptr, (uint32_t) count, pa.finish_geo_first, pa.finish_geo_last, pa.plan, pa.pass,
                            pa.finish_first_ordinary, pa.finish_num_ordinary, s->finish_hint, pa.finish_seq, pa.finish_top_bit,
                            pa.finish_key_bits, long_runs ? 1u : 0u, (uint32_t*) s->finish_crowded.ptr, (uint32_t*) s->finish_outcomes.ptr,
-                           (uint32_t) (sizeof(KeyT) + (VALS ? sizeof(uint32_t) : 0)));
+                           (uint32_t) (sizeof(KeyT) + (VALS ? sizeof(uint32_t) : 0)), pa.narrow_keys ? 1u : 0u);
         HIP_TRY(hipGetLastError());
         if (long_runs)
         {
@@ -262,9 +271,47 @@ glu_status launch_pass_lines(glu_radix_sort_s* s, const KeyT* src_k, const uint3
                                stream));
         if (s->after_histogram_event) HIP_TRY(hipEventRecord(s->after_histogram_event, stream));
     }
-    hipLaunchKernelGGL(scatter, dim3(nb), dim3(G::THREADS), sizeof(Smem), stream, src_k, src_v, dst_k, dst_v,
-                       (const uint32_t*) table, (const uint32_t*) totals, (uint32_t) count, shift, mask, tiles,
-                       (unsigned long long*) nullptr, xform, pa.plan, pa.pass, ranges, share, (const uint32_t*) nullptr, (const uint32_t*) nullptr, 0u, 0u, (const uint32_t*) nullptr);
+    bool both_forms = false;
+    if constexpr (sizeof(KeyT) == 4 && BITS == 8 && !XF && VALS)
+    {
+        // The second top-bit scatter of a sort that may take the narrow hand-off: both forms, of which the device runs one
+        // (PassPlan::narrow) and the other returns at once -- the whole-key form first, in front of the long kernel.  A profile event
+        // between the two lets read_profile book the form that moved the data alone.
+        both_forms = pa.narrow_keys && pa.pair_role == 2 && pa.plan;
+        if (both_forms)
+        {
+            using NarrowSmem = LineSmem<KeyT, BITS, G::THREADS, G::KPT, VALS, true>;
+            // (line stores non-temporal or plain by size, as the pass has them anyway)
+            auto scatter_wide = nt ? lines_scatter_kernel<KeyT, BITS, XF, VALS, true, false, 1>() : lines_scatter_kernel<KeyT, BITS, XF, VALS, false, false, 1>();
+            auto scatter_narrow = nt ? lines_scatter_kernel<KeyT, BITS, XF, VALS, true, false, 2>() : lines_scatter_kernel<KeyT, BITS, XF, VALS, false, false, 2>();
+            static std::once_flag narrow_opt_in;
+            static hipError_t narrow_opt_in_result = hipSuccess;
+            std::call_once(narrow_opt_in, [&] {
+                for (const void* k : {(const void*) lines_scatter_kernel<KeyT, BITS, XF, VALS, true, false, 1>(), (const void*) lines_scatter_kernel<KeyT, BITS, XF, VALS, false, false, 1>()})
+                    if (narrow_opt_in_result == hipSuccess)
+                        narrow_opt_in_result = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) sizeof(Smem));
+                for (const void* k : {(const void*) lines_scatter_kernel<KeyT, BITS, XF, VALS, true, false, 2>(), (const void*) lines_scatter_kernel<KeyT, BITS, XF, VALS, false, false, 2>()})
+                    if (narrow_opt_in_result == hipSuccess)
+                        narrow_opt_in_result = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) sizeof(NarrowSmem));
+            });
+            HIP_TRY(narrow_opt_in_result);
+            hipLaunchKernelGGL(scatter_wide, dim3(nb), dim3(G::THREADS), sizeof(Smem), stream, src_k, src_v, dst_k, dst_v,
+                               (const uint32_t*) table, (const uint32_t*) totals, (uint32_t) count, shift, mask, tiles,
+                               (unsigned long long*) nullptr, xform, pa.plan, pa.pass, ranges, share, (const uint32_t*) nullptr, (const uint32_t*) nullptr, 0u, 0u, (const uint32_t*) nullptr,
+                               (uint16_t*) nullptr);
+            HIP_TRY(hipGetLastError());
+            s->mark_between_forms(stream); // (read_profile books the form that moved the data, not the one that returned at once)
+            hipLaunchKernelGGL(scatter_narrow, dim3(nb), dim3(G::THREADS), sizeof(NarrowSmem), stream, src_k, src_v, dst_k, dst_v,
+                               (const uint32_t*) table, (const uint32_t*) totals, (uint32_t) count, shift, mask, tiles,
+                               (unsigned long long*) nullptr, xform, pa.plan, pa.pass, ranges, share, (const uint32_t*) nullptr, (const uint32_t*) nullptr, 0u, 0u, (const uint32_t*) nullptr,
+                               pa.narrow_keys);
+        }
+    }
+    if (!both_forms)
+        hipLaunchKernelGGL(scatter, dim3(nb), dim3(G::THREADS), sizeof(Smem), stream, src_k, src_v, dst_k, dst_v,
+                           (const uint32_t*) table, (const uint32_t*) totals, (uint32_t) count, shift, mask, tiles,
+                           (unsigned long long*) nullptr, xform, pa.plan, pa.pass, ranges, share, (const uint32_t*) nullptr, (const uint32_t*) nullptr, 0u, 0u, (const uint32_t*) nullptr,
+                           (uint16_t*) nullptr);
     s->mark(stream, true);
     HIP_TRY(hipGetLastError());
     return GLU_OK;

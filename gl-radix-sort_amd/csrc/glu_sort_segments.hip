@@ -80,7 +80,7 @@ glu_status launch_long_run_passes(glu_radix_sort_s* s, KeyT* a_k, uint32_t* a_v,
         hipLaunchKernelGGL(scatter, dim3(nwg), dim3(G::THREADS), sizeof(Smem), stream, (const KeyT*) a_k, (const uint32_t*) a_v, b_k, b_v,
                            (const uint32_t*) table, (const uint32_t*) nullptr, (uint32_t) count, p * 8u, 255u, 0u, (unsigned long long*) nullptr,
                            XF && p + 1 == kPasses ? key_xf << 2 : 0u, const_cast<PassPlan*>(plan), 2u, (const uint2*) image, p,
-                           image + lay.off_first, hdr, 0u, kSegGateIfNot, hdr + 3);
+                           image + lay.off_first, hdr, 0u, kSegGateIfNot, hdr + 3, (uint16_t*) nullptr);
         HIP_TRY(hipGetLastError());
     }
     return GLU_OK;
@@ -132,7 +132,8 @@ glu_status launch_seg_pass(glu_radix_sort_s* s, const uint32_t* src_k, const uin
     s->mark(stream, true);
     hipLaunchKernelGGL(s->nt_stores ? scatter_nt : scatter_plain, dim3(img.nwg), dim3(G::THREADS), sizeof(Smem), stream, src_k, src_v,
                        dst_k, dst_v, (const uint32_t*) table, (const uint32_t*) nullptr, (uint32_t) count, shift, 255u, 0u,
-                       (unsigned long long*) nullptr, 0u, (PassPlan*) nullptr, 0u, subs, 0u, image + img.off_first, gate, gate_cap, gate_mode, (const uint32_t*) nullptr);
+                       (unsigned long long*) nullptr, 0u, (PassPlan*) nullptr, 0u, subs, 0u, image + img.off_first, gate, gate_cap, gate_mode, (const uint32_t*) nullptr,
+                       (uint16_t*) nullptr);
     HIP_TRY(hipGetLastError());
     s->mark(stream, true);
     return GLU_OK;

@@ -38,6 +38,12 @@
 //     front & 3 so that this is aligned on both sides), rebuilds the keys (run's upper bits | field), gathers the four values
 //     by slot, and stores 16 bytes of keys and 16 of values, non-temporal.
 //
+//   * NARROW HAND-OFF (PassPlan::narrow; untyped 4-byte keys with values).  Behind the two top-bit passes a pair's position says what
+//     its top key bits are, so the second scatter may have left only the low 16 bits of every key, in a side array of 2-byte keys
+//     (radix_scatter_lines.hpp, NARROW): the key load is then 8 bytes = 4 keys per lane and piece from that array (same slots), run_hi
+//     comes from the run number, and this kernel writes EVERY key of the key array -- also the key of a run of one pair, and the keys
+//     of a crowded run before it is listed, widened and in the order they have (radix_finish_sort_kernel reads whole keys).
+//
 // In place in the arrays that hold the data after the two top-bit passes (PassPlan::flip[pass]); the geometry comes from the
 // PassPlan as before.  Runs longer than the tile are left to the segmented passes (long_ok) exactly as before.
 #pragma once
@@ -116,7 +122,8 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
                                                                       const uint32_t* __restrict__ starts, uint32_t low_bits,
                                                                       const PassPlan* plan, uint32_t pass, uint32_t geometry,
                                                                       uint32_t key_xf = 0, uint32_t nruns = kFinishRuns,
-                                                                      uint32_t* __restrict__ crowded = nullptr)
+                                                                      uint32_t* __restrict__ crowded = nullptr,
+                                                                      const uint16_t* __restrict__ narrow_keys = nullptr)
 {
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     using Smem = BucketSmem<KeyT, THREADS, KPT, VALS>;
@@ -131,6 +138,11 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
     const KeyCodec<KeyT, XF> codec_out(key_xf);
     if (plan->finish != geometry) return; // (kernel-uniform: the device chose another geometry, or the ordinary passes)
     if (plan->finish_rounds) return;      // (kernel-uniform: few bits to order -- radix_finish_sort_kernel's, behind this kernel)
+    // The narrow hand-off (kernel-uniform, PassPlan::narrow; untyped 4-byte keys with values): the second top-bit scatter left the
+    // values where they are read below and the low 16 bits of every key in narrow_keys[same index]; the key array holds nothing yet.
+    // Every pair's key is rebuilt from its run number and stored by this kernel: the runs of one pair and the crowded runs too.
+    constexpr bool CAN_NARROW = sizeof(KeyT) == 4 && VALS && !XF;
+    const bool narrow = CAN_NARROW && plan->narrow != 0u;
 
     KeyT* const keys = plan->flip[pass] ? keys_b : keys_a;
     uint32_t* const vals = plan->flip[pass] ? vals_b : vals_a;
@@ -146,14 +158,39 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
     {
     const uint32_t begin = starts[run], end = starts[run + 1];
     const uint32_t len = end - begin;
-    if (len == 0 || (!XF && len == 1)) continue; // (workgroup-uniform; a single typed key still has to be decoded)
     if (len > (uint32_t) Smem::TILE) continue;   // (a run longer than the tile: the segmented passes')
+    // (narrow: the key bits from low_bits up -- the run number, and above it what no key differs in)
+    const KeyT narrow_hi = CAN_NARROW ? (KeyT) (((KeyT) run << low_bits) | (KeyT) (plan->narrow & kPlanNarrowHiMask)) : (KeyT) 0;
+    if (CAN_NARROW && narrow && len == 1)
+    {
+        if (tid == 0) keys[begin] = (KeyT) (narrow_hi | (KeyT) narrow_keys[begin]); // (its value lies where it belongs)
+        continue;
+    }
+    if (len == 0 || (!XF && len == 1)) continue; // (workgroup-uniform; a single typed key still has to be decoded)
     const uint32_t front = begin & 31u, f4 = front & 3u;
     const uint32_t abegin = begin - front;
     const uint32_t total = front + len; // slots [front, total) hold the run
 
     // ---- load: 16 bytes per lane and piece, keys and values into registers (the values wait there until the words are in order)
     u32x4_t kraw[KV];
+    if (CAN_NARROW && narrow) // (kernel-uniform: one branch around the loads, none inside them)
+    {
+        // 8 bytes = the piece's four 2-byte keys, in .x and .y until the words are made (every element below n was written by this
+        // sort's narrow scatter: what lies in front of and behind the run in its first and last piece is the neighbouring runs')
+        typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int r = 0; r < KV; r++)
+        {
+            const uint32_t q = r * THREADS + tid, e0 = abegin + q * 4u;
+            kraw[r] = u32x4_t{0u, 0u, 0u, 0u};
+            if (q * 4u < total && e0 + 4u <= n)
+            {
+                const u32x2_t h = *reinterpret_cast<const u32x2_t*>(narrow_keys + e0);
+                kraw[r].x = h.x, kraw[r].y = h.y;
+            }
+        }
+    }
+    else
 #pragma unroll
     for (int r = 0; r < KV; r++)
     {
@@ -199,7 +236,19 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
             {
                 KeyT t[EPV];
 #pragma unroll
-                for (int e = 0; e < EPV; e++) t[e] = e0 + e < n ? keys[e0 + e] : (KeyT) 0;
+                for (int e = 0; e < EPV; e++) t[e] = (KeyT) 0;
+                if (CAN_NARROW && narrow) // (the same two words as a whole piece of 2-byte keys)
+                {
+                    uint32_t h[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) h[e] = e0 + e < n ? (uint32_t) narrow_keys[e0 + e] : 0u;
+                    t[0] = (KeyT) (h[0] | (h[1] << 16)), t[1] = (KeyT) (h[2] | (h[3] << 16));
+                }
+                else
+                {
+#pragma unroll
+                    for (int e = 0; e < EPV; e++) t[e] = e0 + e < n ? keys[e0 + e] : (KeyT) 0;
+                }
                 __builtin_memcpy(&kraw[r], t, 16);
             }
         }
@@ -216,6 +265,25 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
     const uint32_t wave_s = (uint32_t) __builtin_amdgcn_readfirstlane((int) wave);
     auto live = [&](int r) { return (r * THREADS + wave_s * kWave) * EPV < total; };
     WordT word[ITEMS];
+    constexpr int NARROW_EPV = CAN_NARROW ? 4 : 0; // (2-byte keys per piece)
+    if (CAN_NARROW && narrow) // (kernel-uniform)
+    {
+#pragma unroll
+        for (int r = 0; r < KV; r++)
+        {
+            const uint32_t h[2] = {kraw[r].x, kraw[r].y};
+#pragma unroll
+            for (int e = 0; e < NARROW_EPV; e++) // (no iteration in the instantiations that cannot take the narrow hand-off)
+            {
+                const uint32_t slot = (r * THREADS + tid) * 4u + e;
+                const bool valid = slot >= front && slot < total;
+                const uint32_t low = (e & 1) ? h[e >> 1] >> 16 : h[e >> 1] & 0xFFFFu;
+                word[r * EPV + e] = valid ? (WordT) (((WordT) (low & (uint32_t) low_mask) << SB) | (WordT) slot) : INVALID;
+            }
+        }
+        if (tid == 0) s.run_hi = narrow_hi;
+    }
+    else
 #pragma unroll
     for (int r = 0; r < KV; r++)
     {
@@ -285,6 +353,13 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
     __syncthreads();
     if (s.crowded != 0u) // (workgroup-uniform) radix_finish_sort_kernel's, launched behind this kernel; nothing has been stored
     {
+        if constexpr (CAN_NARROW)
+        {
+            // narrow: radix_finish_sort_kernel reads whole keys from the key array -- the run's are written there now, in the order
+            // they have (this cold loop, not that kernel's load, knows of the side array: the uncrowded path keeps its registers)
+            if (narrow)
+                for (uint32_t i = tid; i < len; i += THREADS) keys[begin + i] = (KeyT) (narrow_hi | (KeyT) narrow_keys[begin + i]);
+        }
         if (tid == 0) crowded_list_append(crowded, nruns, run);
         if (LOOP) __syncthreads();
         continue;

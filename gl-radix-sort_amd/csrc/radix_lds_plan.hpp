@@ -315,7 +315,8 @@ static __global__ __launch_bounds__(1024) void radix_finish_plan_kernel(const ui
                                                                  uint32_t first_ordinary, uint32_t num_ordinary,
                                                                  uint32_t* hint, uint32_t attempt, uint32_t top_bit,
                                                                  uint32_t key_bits, uint32_t long_ok, uint32_t* crowded_lists,
-                                                                 uint32_t* outcomes = nullptr, uint32_t pair_bytes = 8)
+                                                                 uint32_t* outcomes = nullptr, uint32_t pair_bytes = 8,
+                                                                 uint32_t narrow_ok = 0)
 {
     __shared__ uint32_t tmp[3][16];
     __shared__ uint32_t over_tmp[2][kFinishGeometries][16];
@@ -441,6 +442,15 @@ static __global__ __launch_bounds__(1024) void radix_finish_plan_kernel(const ui
             const uint64_t low_mask = low_bits >= 64u ? ~0ull : (1ull << low_bits) - 1ull;
             const uint32_t to_order = plan->bits_valid ? (uint32_t) __popcll(varying & low_mask) : low_bits;
             plan->finish_rounds = to_order < 9u ? 1u : 0u;
+            // The narrow hand-off (PassPlan::narrow): the bucket kernel takes EVERY run -- no ballot rounds, no run longer than the
+            // tile (the segmented passes read whole keys from the key array) -- and at most 16 bits are left below the runs' bits.
+            // (Both top-bit scatters then move data: n >= 2^22 pairs in runs of at most 9216 fill more than 256 runs, so neither of
+            // the runs' two digits is constant.)
+            const bool narrow = accept && narrow_ok != 0u && to_order >= 9u && longest <= finish_geometry_capacity(geo) && low_bits <= 16u;
+            // (bits_or: every key's OR -- from top_bit up all keys agree, so it is their common value there)
+            const uint32_t common_hi = plan->bits_valid && top_bit < 32u ? plan->bits_or[0] & ~((1u << top_bit) - 1u) : 0u;
+            plan->narrow = narrow ? 1u | (common_hi & kPlanNarrowHiMask) : 0u;
+            if (outcomes) outcomes[256u + (attempt & 255u)] = (attempt << 1) | (narrow ? 1u : 0u); // (glu_radix_sort_read_profile)
         }
         // for the host, which reads it without synchronising (pinned host memory): the outcome of attempt number `attempt` --
         // attempt << 3 | the geometry chosen, 0 = refused, stored LAST and with release: the host reads it first, then which key

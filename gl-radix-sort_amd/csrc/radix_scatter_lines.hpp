@@ -31,9 +31,15 @@ namespace glu_hip
 template<typename KeyT>
 constexpr int line_elems() { return 128 / (int) sizeof(KeyT); }
 
-template<typename KeyT, int BITS, int THREADS, int KPT, bool VALS = true>
+// NARROW (the second top-bit pass of a sort that ends in LDS, narrow hand-off: DESIGN.md section 4.4): only the low 16 key bits are
+// staged -- 6 bytes per staged pair instead of 8 -- and leave as 2-byte keys, 64 bytes per granule: HALF a line, so the key stream
+// is the shadowed one (below), as the value stream is for 8-byte keys.
+template<typename KeyT, int BITS, int THREADS, int KPT, bool VALS = true, bool NARROW = false>
 struct LineSmem
 {
+    static_assert(!NARROW || (sizeof(KeyT) == 4 && VALS), "the narrow hand-off: 4-byte keys with values");
+    using StageT = typename std::conditional<NARROW, uint16_t, KeyT>::type;   // what a staged key is
+    using ShadowT = typename std::conditional<NARROW, uint16_t, uint32_t>::type; // an element of the shadowed stream
     static constexpr int RADIX = 1 << BITS;
     static constexpr int WAVES = THREADS / kWave;
     static constexpr int TILE = THREADS * KPT;
@@ -47,7 +53,7 @@ struct LineSmem
     static constexpr int MAXLINES = (TILE + RADIX * (LINE - 1)) / LINE + 2;
     static_assert(TILE < 65536 && MAXLINES < 65536, "ranked positions and line numbers share one 32-bit scan word");
     static_assert(RADIX <= 256, "the line table holds digits as bytes");
-    PairArray<KeyT, TILE + CARRY, VALS> buf; // [0, TILE): the tile in ranked order;  [TILE + d * CSTRIDE, + LINE): carry of digit d
+    PairArray<StageT, TILE + CARRY, VALS> buf; // [0, TILE): the tile in ranked order;  [TILE + d * CSTRIDE, + LINE): carry of digit d
     // 16-bit counters (a wave ranks at most 64 * KPT elements of a tile, positions stay below TILE < 65536): half the LDS
     // of 32-bit ones, which the tile gets.  Rows of RADIX + 4 halfwords: the scan's four rows per thread land 8 banks apart.
     static constexpr int WCNT_STRIDE = RADIX + 4;
@@ -60,8 +66,11 @@ struct LineSmem
     // line a digit emits in a tile is the first half of a value line (its second half follows a tile period later, when the
     // L2 has long dropped the half-written line: fill reads, traffic 1.13 x algorithmic), its 16 values wait here instead
     // and leave together with the second half.
-    static constexpr bool SHADOW = sizeof(KeyT) == 8 && VALS;
-    uint32_t shadow[SHADOW ? RADIX * LINE : 1];
+    // NARROW: the same for the 2-byte KEYS of 4-byte-key pairs (a granule of 32 elements is a whole line of values and half a line of
+    // keys): the shadow serves whichever stream has half lines.
+    static constexpr bool SHADOW = (sizeof(KeyT) == 8 && VALS) || NARROW;
+    static_assert(!SHADOW || LINE * sizeof(ShadowT) == 64, "a shadowed granule is half a line: four 16-byte pieces");
+    alignas(16) ShadowT shadow[SHADOW ? RADIX * LINE : 1];
     uint32_t shadow_out[SHADOW ? RADIX : 1]; // global index of the shadowed line that leaves in this tile's scan phase, or ~0
     uint8_t ltab[(MAXLINES + 3) & ~3]; // digit of every line written this tile
     uint32_t scan_tmp[WAVES];
@@ -92,15 +101,22 @@ struct LineSmem
 // (sub-block, digit) range -- is the pass as above; `totals`, `plan`, `share` are not used.
 template<typename KeyT, int BITS, int THREADS, int KPT, bool XF = false, bool VALS = true, int ABLATE = 0, bool STAMPS = false,
          int RANK_SPLIT = (KPT + 2) / 3, bool STAGGER = true, bool NT_STORES = false, int PRIO = 0, bool SEG = false,
-         bool RANK_ATOMIC = false, bool BEHIND_ATTEMPT = false>
+         bool RANK_ATOMIC = false, bool BEHIND_ATTEMPT = false, int NARROW = 0>
 __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
     const KeyT* __restrict__ keys_a, const uint32_t* __restrict__ vals_a, KeyT* __restrict__ keys_b,
     uint32_t* __restrict__ vals_b, const uint32_t* __restrict__ table, const uint32_t* __restrict__ totals, uint32_t n,
     uint32_t shift, uint32_t mask, uint32_t tiles_total, unsigned long long* stamps = nullptr, uint32_t xform = 0,
     PassPlan* plan = nullptr, uint32_t pass = 0, const uint2* __restrict__ ranges = nullptr, uint32_t share = 0,
     const uint32_t* __restrict__ seg_first = nullptr, const uint32_t* gate = nullptr, uint32_t gate_cap = 0, uint32_t gate_mode = 0,
-    const uint32_t* seg_shares = nullptr)
+    const uint32_t* seg_shares = nullptr, uint16_t* __restrict__ narrow_keys = nullptr)
 {
+    // NARROW (the second top-bit pass of a sort that may hand 2-byte keys to its in-LDS pass; both forms are enqueued and
+    // PassPlan::narrow, set by radix_finish_plan_kernel before anything moved, says which runs -- the other returns at once):
+    //   1 = the pass as ever, unless the plan says narrow;
+    //   2 = the narrow form: values to vals_b / vals_a as ever, the low 16 bits of every key to narrow_keys[same index].
+    static_assert(NARROW == 0 || (!SEG && !XF && VALS && sizeof(KeyT) == 4), "the narrow hand-off: untyped 4-byte keys with values");
+    constexpr bool NARROW_OUT = NARROW == 2;
+    if (NARROW != 0 && (plan->narrow != 0u) != NARROW_OUT) return; // (kernel-uniform)
     // (SEG: a pass of a segmented sort that may end in LDS runs or returns by the longest run, radix_seg_passes.hpp)
     if (SEG && gate_mode != 0 && ((*gate <= gate_cap) != (gate_mode == 1))) return; // (kernel-uniform)
     const KeyT* __restrict__ src_keys = keys_a;
@@ -131,7 +147,15 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
             dst_vals = const_cast<uint32_t*>(vals_a);
         }
     }
-    using Smem = LineSmem<KeyT, BITS, THREADS, KPT, VALS>;
+    using Smem = LineSmem<KeyT, BITS, THREADS, KPT, VALS, NARROW_OUT>;
+    using StageT = typename Smem::StageT;
+    using ShadowT = typename Smem::ShadowT;
+    // the stream whose granules are half lines (SHADOW): the values of 8-byte keys, the 2-byte keys of the narrow form
+    ShadowT* const shadow_dst = [&]() {
+        if constexpr (NARROW_OUT) return narrow_keys;
+        else return dst_vals;
+    }();
+    constexpr uint32_t SHADOW_PIECE = 16 / sizeof(ShadowT); // elements of the shadowed stream per 16-byte piece
     constexpr int RADIX = Smem::RADIX;
     constexpr int WAVES = Smem::WAVES;
     constexpr int TILE = Smem::TILE;
@@ -143,6 +167,15 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem& s = *reinterpret_cast<Smem*>(smem_raw);
+    // (the per-wave totals of the two block scans.  The narrow form keeps them in static LDS, in front of the dynamic block: at the
+    // end of the 144 KB block their addresses are beyond a DS instruction's 16-bit offset, and the two registers that then hold
+    // them were the narrow form's only spills)
+    uint32_t* scan_tmp = s.scan_tmp;
+    if constexpr (NARROW_OUT)
+    {
+        __shared__ uint32_t narrow_scan_tmp[WAVES];
+        scan_tmp = narrow_scan_tmp;
+    }
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t nb = gridDim.x, b = blockIdx.x;
@@ -155,6 +188,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
     uint32_t carry_start = 0; // 32-aligned global index of the digit's first carried element; carried = digit_base - carry_start
     uint32_t owned_from = 0;  // first global index of the digit inside this workgroup's range
     constexpr bool SHADOW = Smem::SHADOW;
+    constexpr uint32_t ORPHAN_SHIFT = LINE == 16 ? 20u : 21u; // dinfo.z: first line | carried << 16 | (SHADOW) orphan line << ORPHAN_SHIFT
     bool shadow_valid = false; // SHADOW: s.shadow[sd] holds the values of the line at global index shadow_pos (keys written already)
     uint32_t shadow_pos = 0;
 
@@ -197,9 +231,9 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
         const uint32_t t = digit_owner ? totals[sd] : 0u;
         uint32_t wtotal;
         uint32_t excl = wave_exclusive_sum(t, lane, wtotal);
-        if (lane == 0) s.scan_tmp[wave] = wtotal;
+        if (lane == 0) scan_tmp[wave] = wtotal;
         __syncthreads();
-        excl += sum_of_preceding_waves(s.scan_tmp, WAVES, wave, lane);
+        excl += sum_of_preceding_waves(scan_tmp, WAVES, wave, lane);
         if (digit_owner)
         {
             digit_base = excl + table[(size_t) sd * nb + b];
@@ -321,7 +355,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                 const uint32_t d = item / (LINE / 4), s0 = (item % (LINE / 4)) * 4;
                 const uint32_t t = s.tail[d];
                 const uint32_t from = t & 0xFFFFu, lo = (t >> 16) & 0xFFu, hi = t >> 24;
-                KeyT k[4];
+                StageT k[4];
                 uint32_t v[4];
                 // slots below lo read the element of slot lo (a valid position), slots from hi up read past the run
                 // (inside the buffer): neither is written.  (`from` is the ranked position of slot 0 modulo 2^16: it lies
@@ -392,7 +426,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                 }
                 uint32_t wtotal;
                 excl = wave_exclusive_sum(n_raw | (nl_d << 16), lane, wtotal);
-                if (lane == 0) s.scan_tmp[wave] = wtotal;
+                if (lane == 0) scan_tmp[wave] = wtotal;
             }
             __syncthreads();
             if (SHADOW && wave >= SCAN_WAVES)
@@ -402,24 +436,24 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                 // (One thread per digit storing its 64 bytes with four instructions made the pass 30 % slower: every
                 // instruction then writes 16 bytes each of 64 different lines.)
                 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                constexpr uint32_t TT = THREADS - SCAN_WAVES * kWave, ITEMS = RADIX * (LINE / 4);
+                constexpr uint32_t TT = THREADS - SCAN_WAVES * kWave, ITEMS = RADIX * 4;
                 for (uint32_t item = tid - SCAN_WAVES * kWave; item < ITEMS; item += TT)
                 {
-                    const uint32_t d = item / (LINE / 4), q = item % (LINE / 4);
+                    const uint32_t d = item / 4, q = item % 4;
                     const uint32_t out = s.shadow_out[d];
                     if (out != 0xFFFFFFFFu)
                     {
-                        const u32x4_t vv = *reinterpret_cast<const u32x4_t*>(&s.shadow[d * LINE + q * 4]);
+                        const u32x4_t vv = *reinterpret_cast<const u32x4_t*>(&s.shadow[d * LINE + q * SHADOW_PIECE]);
                         if (NT_STORES)
-                            __builtin_nontemporal_store(vv, reinterpret_cast<u32x4_t*>(dst_vals + out + 4 * q));
+                            __builtin_nontemporal_store(vv, reinterpret_cast<u32x4_t*>(shadow_dst + out + SHADOW_PIECE * q));
                         else
-                            *reinterpret_cast<u32x4_t*>(dst_vals + out + 4 * q) = vv;
+                            *reinterpret_cast<u32x4_t*>(shadow_dst + out + SHADOW_PIECE * q) = vv;
                     }
                 }
             }
             if (wave < SCAN_WAVES)
             {
-                if (SCAN_WAVES > 1) excl += sum_of_preceding_waves(s.scan_tmp, SCAN_WAVES, wave, lane);
+                if (SCAN_WAVES > 1) excl += sum_of_preceding_waves(scan_tmp, SCAN_WAVES, wave, lane);
                 const uint32_t pos = excl & 0xFFFFu, line0 = excl >> 16;
                 if (digit_owner)
                 {
@@ -434,7 +468,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                     uint32_t orphan_line = 0x3FFu; // SHADOW: the line (index in this tile's line table) whose values go to s.shadow
                     if (SHADOW)
                     {
-                        static_assert(!SHADOW || (Smem::MAXLINES < 0x3FF && LINE == 16), "line numbers in 10 bits, carried count in 4");
+                        static_assert(!SHADOW || (Smem::MAXLINES < 0x3FF && (LINE == 16 || LINE == 32)), "line numbers in 10 bits, carried count in 4 or 5");
                         if (shadow_valid && nl_d > 0) shadow_valid = false; // (its values are leaving: the other waves, above)
                         if (nl_d > 0)
                         {
@@ -447,7 +481,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                             }
                         }
                     }
-                    s.dinfo[sd] = make_uint4(carry_start, pos - c_d, line0 | (c_d << 16) | (SHADOW ? orphan_line << 20 : 0u), owned_from);
+                    s.dinfo[sd] = make_uint4(carry_start, pos - c_d, line0 | (c_d << 16) | (SHADOW ? orphan_line << ORPHAN_SHIFT : 0u), owned_from);
                     s.tail[sd] = ((pos + n_d - c_new) & 0xFFFFu) | ((c_new - k) << 16) | (c_new << 24);
                     digit_base += n_d;
                     carry_start += nl_d * LINE;
@@ -482,7 +516,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
             for (int i = 0; i < KPT; i++)
             {
                 const uint32_t pos = rank[i] + my_cnt[digit_of<KeyT>(key[i], shift, MASK)];
-                s.buf.put(pos, key[i], VALS ? val[i] : 0u);
+                s.buf.put(pos, (StageT) key[i], VALS ? val[i] : 0u);
                 if (VALS) val[i] = src_vals[next_base + i * kWave];
             }
             if (PRIO & 1) __builtin_amdgcn_s_setprio(0);
@@ -521,7 +555,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
             {
                 uint32_t g0[QB], from_run[QB], from_carry[QB], owned[QB];
                 int in_carry[QB];
-                int to_shadow[SHADOW ? QB : 1]; // SHADOW: >= 0: the quad's values go to these shadow slots, not to memory
+                int to_shadow[SHADOW ? QB : 1]; // SHADOW: >= 0: the quad's elements of the shadowed stream go to these shadow slots, not to memory
 #pragma unroll
                 for (int u = 0; u < QB; u++)
                 {
@@ -530,8 +564,8 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                     const uint32_t l = qi / (LINE / 4), sub = qi % (LINE / 4);
                     const uint32_t d = s.ltab[l];
                     const uint4 info = s.dinfo[d];
-                    const uint32_t line0 = info.z & 0xFFFFu, carried = SHADOW ? (info.z >> 16) & 0xFu : info.z >> 16;
-                    if (SHADOW) to_shadow[u] = l == ((info.z >> 20) & 0x3FFu) ? (int) (d * LINE + sub * 4) : -1;
+                    const uint32_t line0 = info.z & 0xFFFFu, carried = SHADOW ? (info.z >> 16) & (LINE - 1u) : info.z >> 16;
+                    if (SHADOW) to_shadow[u] = l == ((info.z >> ORPHAN_SHIFT) & 0x3FFu) ? (int) (d * LINE + sub * 4) : -1;
                     const uint32_t q0 = (l - line0) * LINE + sub * 4; // index in (carry ++ run) of the quad's first element
                     g0[u] = info.x + q0;                               // its global index (a multiple of 4)
                     from_run[u] = info.y + q0;                         // ranked position, were it an element of the run
@@ -542,17 +576,33 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
 #pragma unroll
                 for (int u = 0; u < QB; u++)
                 {
-                    KeyT k[4];
+                    StageT k[4];
                     uint32_t v[4];
 #pragma unroll
                     for (int e = 0; e < 4; e++) s.buf.get((e < in_carry[u] ? from_carry[u] : from_run[u]) + e, k[e], v[e]);
+                    if constexpr (!NARROW_OUT)
+                    {
 #pragma unroll
-                    for (int e = 0; e < 4; e++) k[e] = codec_out.decode(k[e]);
+                        for (int e = 0; e < 4; e++) k[e] = codec_out.decode(k[e]);
+                    }
                     const bool real = u == 0 || q_first + u * THREADS < quads;
                     if (real && g0[u] >= owned[u] && (ABLATE == 0 || g0[u] + 3 < n))
                     {
                         typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                        if constexpr (sizeof(KeyT) == 4)
+                        if constexpr (NARROW_OUT)
+                        {
+                            // four 2-byte keys: 8 bytes per lane, the 8 lanes of a line 64 -- half a line, which leaves beside its
+                            // other half (the neighbouring lanes' of this instruction) or waits for it in the shadow
+                            typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+                            const u32x2_t kk = {(uint32_t) k[0] | ((uint32_t) k[1] << 16), (uint32_t) k[2] | ((uint32_t) k[3] << 16)};
+                            if (to_shadow[u] >= 0)
+                                *reinterpret_cast<u32x2_t*>(&s.shadow[to_shadow[u]]) = kk; // (a fully owned line: see the scan phase)
+                            else if (NT_STORES)
+                                __builtin_nontemporal_store(kk, reinterpret_cast<u32x2_t*>(narrow_keys + g0[u]));
+                            else
+                                *reinterpret_cast<u32x2_t*>(narrow_keys + g0[u]) = kk;
+                        }
+                        else if constexpr (sizeof(KeyT) == 4)
                         {
                             u32x4_t kk = {(uint32_t) k[0], (uint32_t) k[1], (uint32_t) k[2], (uint32_t) k[3]};
                             if (NT_STORES)
@@ -578,7 +628,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                         if (VALS)
                         {
                             u32x4_t vv = {v[0], v[1], v[2], v[3]};
-                            if (SHADOW && to_shadow[u] >= 0)
+                            if (SHADOW && !NARROW_OUT && to_shadow[u] >= 0)
                                 *reinterpret_cast<u32x4_t*>(&s.shadow[to_shadow[u]]) = vv; // (a fully owned line: see the scan phase)
                             else if (NT_STORES)
                                 __builtin_nontemporal_store(vv, reinterpret_cast<u32x4_t*>(dst_vals + g0[u]));
@@ -594,7 +644,8 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
                         for (int e = 0; e < 4; e++)
                             if (g0[u] + e >= owned[u])
                             {
-                                dst_keys[g0[u] + e] = k[e];
+                                if constexpr (NARROW_OUT) narrow_keys[g0[u] + e] = k[e];
+                                else dst_keys[g0[u] + e] = k[e];
                                 if (VALS) dst_vals[g0[u] + e] = v[e];
                             }
                     }
@@ -638,7 +689,7 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
         typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         const u32x4_t* sh = reinterpret_cast<const u32x4_t*>(&s.shadow[sd * LINE]);
 #pragma unroll
-        for (int q = 0; q < (int) LINE / 4; q++) *reinterpret_cast<u32x4_t*>(dst_vals + shadow_pos + 4 * q) = sh[q];
+        for (int q = 0; q < 4; q++) *reinterpret_cast<u32x4_t*>(shadow_dst + shadow_pos + SHADOW_PIECE * q) = sh[q];
         shadow_valid = false;
     }
     if (ABLATE < 4)
@@ -650,10 +701,11 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_lines_kernel(
             const uint32_t g = info.x + slot;
             if (slot < info.y && g >= info.w && (ABLATE == 0 || g < n))
             {
-                KeyT k;
+                StageT k;
                 uint32_t v;
                 s.buf.get((uint32_t) TILE + d * CSTRIDE + slot, k, v);
-                dst_keys[g] = codec_out.decode(k);
+                if constexpr (NARROW_OUT) narrow_keys[g] = k;
+                else dst_keys[g] = codec_out.decode(k);
                 if (VALS) dst_vals[g] = v;
             }
         }

@@ -183,11 +183,17 @@ struct alignas(64) PassPlan
     uint32_t shift_down[kPlanMaxPasses];
     // (radix_sample_top_kernel's workgroups: OR of the sampled keys, OR of their complements, low / high word; workgroups done)
     uint32_t sample_or[2], sample_nor[2], sample_done;
+    // narrow != 0 (radix_finish_plan_kernel, before anything moves): the second top-bit scatter hands the in-LDS pass the low 16 bits
+    // of every key in a side array of 2-byte keys instead of whole keys in the key array -- a pair's position says what its other
+    // key bits are: the run number, and the key bits from top_bit (>= 16) up, which no key differs in.  Bit 0: the flag; bits
+    // [16, 32): those common key bits (kPlanNarrowHiMask).  One word: it is the last of the plan's 768 bytes.  Zeroed with pair_fallback.
+    uint32_t narrow;
 };
 
 // PassPlan::skip values: 0 = the pass runs, 1 = an identity found by the row scan (one digit value holds every key; the
 // tables of the pass are complete), kSkipWithoutCounting = an identity known before counting (no tables)
 constexpr uint32_t kSkipWithoutCounting = 2;
+constexpr uint32_t kPlanNarrowHiMask = 0xFFFF0000u; // PassPlan::narrow
 
 // flags of the count kernels of planned sorts
 constexpr uint32_t kPlanCollectBits = 1; // first pass of an untyped sort: collect which key bits vary
@@ -727,6 +733,24 @@ struct PairArray<uint64_t, COUNT, true>
         vals[pos] = v;
     }
     __device__ __forceinline__ void get(uint32_t pos, uint64_t& k, uint32_t& v) const
+    {
+        k = keys[pos];
+        v = vals[pos];
+    }
+};
+
+// 2-byte keys (the low half of a 4-byte key: the narrow form of radix_scatter_lines_kernel) beside their values: 6 bytes per pair
+template<int COUNT>
+struct PairArray<uint16_t, COUNT, true>
+{
+    uint32_t vals[COUNT];
+    uint16_t keys[COUNT];
+    __device__ __forceinline__ void put(uint32_t pos, uint16_t k, uint32_t v)
+    {
+        keys[pos] = k;
+        vals[pos] = v;
+    }
+    __device__ __forceinline__ void get(uint32_t pos, uint16_t& k, uint32_t& v) const
     {
         k = keys[pos];
         v = vals[pos];

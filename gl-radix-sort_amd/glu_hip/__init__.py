@@ -88,6 +88,7 @@ SYMBOLS = [
                                                   _P(ctypes.c_double), _P(_u64)]),
     ("glu_radix_sort_plan_finish", _int, [_sz, _u32, _P(_u32), _P(_u32)]),
     ("glu_radix_sort_read_finish", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
+    ("glu_radix_sort_read_handoff", _int, [_vp, _P(_u32)]),
     ("glu_radix_sort_read_long_runs", _int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_radix_sort_read_seg_finish", _int, [_vp, _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32), _P(_u32)]),
     ("glu_radix_sort_run_batch_ptr", _int, [_vp, _vp, _vp, _sz, _sz, _int, _vp]),
@@ -635,6 +636,13 @@ class RadixSort(_Handle):
         check(lib().glu_radix_sort_read_finish(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
                                                ctypes.byref(e)))
         return {"attempted": a.value, "accepted": b.value, "longest_run": c.value, "capacity": d.value, "top_bit": e.value}
+
+    def read_handoff(self):
+        """{narrow}: 1 if the last sort handed its in-LDS pass 2-byte keys in the object's side array (glu_radix_sort_read_handoff);
+        synchronise first."""
+        a = _u32(0)
+        check(lib().glu_radix_sort_read_handoff(self._h, ctypes.byref(a)))
+        return {"narrow": a.value}
 
     def read_long_runs(self):
         """{runs, sub_blocks, pairs}: what the last sort that ended in LDS gave to the segmented passes for runs longer than the tile

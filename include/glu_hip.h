@@ -322,6 +322,15 @@ GLU_API glu_status glu_radix_sort_plan_finish(size_t count, uint32_t key_bytes, 
  * GLU_HIP_SORT_LDS_FINISH=0 in the environment of glu_radix_sort_create switches the attempt off.  Any pointer may be NULL. */
 GLU_API glu_status glu_radix_sort_read_finish(glu_radix_sort sort, uint32_t* attempted, uint32_t* accepted,
                                               uint32_t* longest_run, uint32_t* capacity, uint32_t* top_bit);
+/* The narrow hand-off of a sort that ends in LDS (untyped 32-bit keys with values).  Behind the two counting passes a pair's position
+ * says what its top key bits are, so the second of them hands the in-LDS pass only the low 16 bits of every key, in a side array of
+ * n x 2 bytes in the object's scratch (reserved by glu_radix_sort_prepare, or by the first sort, for counts at which the attempt is
+ * made): 48.25 instead of 52.25 bytes of memory traffic per pair.  The device decides (before anything moves) for it when the sort
+ * ends in LDS, no run is longer than the tile and the in-LDS pass orders the runs by its bucket round; every other sort hands over
+ * whole keys in the key array, as before.  narrow = 1: the last sort on the object took the narrow hand-off (the caller has
+ * synchronised its stream).  GLU_HIP_SORT_NARROW_HANDOFF=0 (environment of glu_radix_sort_create, or glu_radix_sort_set_option BEFORE
+ * the object's scratch is prepared: it decides the side array's allocation) switches it off. */
+GLU_API glu_status glu_radix_sort_read_handoff(glu_radix_sort sort, uint32_t* narrow);
 /* Runs LONGER than the tile of the in-LDS pass (round 5; 4-byte untyped keys with values): they no longer send the whole sort back
  * to the ordinary passes -- the device lists them as segments, two segmented counting passes (the reference's pass per segment,
  * glu/RadixSort.hpp:142-182) order just their elements by the low 16 key bits, and the in-LDS pass takes every other run.  The

@@ -121,7 +121,7 @@ void run(uint32_t log2n, uint32_t mode, uint32_t low_bits, uint32_t geo)
                                    (unsigned long long*) nullptr, (const uint32_t*) nullptr, 0u);
             else
                 hipLaunchKernelGGL(kern_new, dim3(nruns), dim3(THREADS), sizeof(SmemNew), 0, keys, vals, keys, vals, (const uint32_t*) d_starts,
-                                   low_bits, (const PassPlan*) plan, 0u, geo, 0u, nruns, d_flags);
+                                   low_bits, (const PassPlan*) plan, 0u, geo, 0u, nruns, d_flags, (const uint16_t*) nullptr);
             CK(hipEventRecord(e1, 0));
             if (which == 1) // the runs the bucket kernel listed: round 5's kernel, 8192 workgroups that loop over the list
                 hipLaunchKernelGGL(kern_crowded, dim3(8192), dim3(THREADS), sizeof(SmemOld), 0, keys, vals, keys, vals, (const uint32_t*) d_starts,
