@@ -1,13 +1,16 @@
 // glu_merge.hip -- merge of libglu_hip.so (merge_kernels.hpp): glu_merge_create, glu_merge_destroy, glu_merge_prepare,
-// glu_merge_run_ptr, glu_merge_plan, glu_merge_last; and the set operations on merge's tiles (set_ops_kernels.hpp):
+// glu_merge_run_ptr, glu_merge_plan, glu_merge_last, and the batched merge (merge_batch_kernels.hpp): glu_merge_prepare_batch,
+// glu_merge_run_batch_offsets_ptr, glu_merge_run_batch_ptr, glu_merge_plan_batch; and the set operations on merge's tiles (set_ops_kernels.hpp):
 // glu_set_ops_create, glu_set_ops_destroy, glu_set_ops_prepare, glu_set_ops_run_ptr, glu_set_ops_plan, glu_set_ops_last.
 // The library's other translation units: glu_host.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "glu_batch_host.hpp"
 #include "glu_merge_object.hpp"
 #include "glu_set_ops_object.hpp"
+#include "merge_batch_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "set_ops_kernels.hpp"
 
@@ -58,6 +61,99 @@ glu_status run(glu_merge_s* s, const void* a_keys, const uint32_t* a_vals, size_
     m.tiles = p.tiles;
     m.split = (uint32_t*) s->split.ptr;
     return launch<K>(m, p, out_vals != nullptr, stream);
+}
+
+// ---- the batched merge
+struct BatchCall
+{
+    const void *a_keys, *b_keys;
+    const uint32_t *a_vals, *b_vals;
+    const uint32_t *a_offsets, *b_offsets; // NULL: equal partitions of a_len and b_len
+    size_t a_len, b_len, a_total, b_total, num_segments;
+    void* out_keys;
+    uint32_t *out_vals, *out_offsets;
+    int key_type;
+    void* stream;
+};
+
+template<typename K>
+glu_status run_batch(glu_merge_s* s, const BatchCall& c, const MergePlan& p, hipStream_t stream)
+{
+    MergeBatchArgs<K> m = {};
+    m.a_keys = (const K*) c.a_keys;
+    m.b_keys = (const K*) c.b_keys;
+    m.a_vals = c.a_vals;
+    m.b_vals = c.b_vals;
+    m.out_keys = (K*) c.out_keys;
+    m.out_vals = c.out_vals;
+    m.a_offsets = c.a_offsets;
+    m.b_offsets = c.b_offsets;
+    m.a_len = (uint32_t) c.a_len;
+    m.b_len = (uint32_t) c.b_len;
+    m.a_total = (uint32_t) c.a_total;
+    m.b_total = (uint32_t) c.b_total;
+    m.num_segments = (uint32_t) c.num_segments;
+    m.xf = key_xf_of(c.key_type);
+    m.tiles = p.tiles;
+    m.seg_steps = merge_steps(m.num_segments - 1u);
+    m.split_steps = merge_steps(std::min(m.a_total, m.b_total));
+    m.bounds = (MergeBatchBoundary*) s->split.ptr;
+    m.out_offsets = c.out_offsets;
+    // one thread per tile boundary and per out_offsets entry
+    const uint32_t threads = std::max<uint32_t>(p.tiles, c.out_offsets ? m.num_segments : 0u);
+    hipLaunchKernelGGL((merge_batch_partition_kernel<K>), dim3(threads / kMergeThreads + 1), dim3(kMergeThreads), 0, stream, m, p.tile);
+    HIP_TRY(hipGetLastError());
+    if (!p.tiles) return GLU_OK;
+    if (c.out_vals)
+        hipLaunchKernelGGL((merge_batch_tile_kernel<K, true>), dim3(p.tiles), dim3(kMergeThreads), 0, stream, m);
+    else
+        hipLaunchKernelGGL((merge_batch_tile_kernel<K, false>), dim3(p.tiles), dim3(kMergeThreads), 0, stream, m);
+    HIP_TRY(hipGetLastError());
+    return GLU_OK;
+}
+
+// Both forms of the batched call behind their own checks of the segments' shape.
+glu_status merge_batch(glu_merge merge, BatchCall c)
+{
+    GLU_TRY(check_total(c.a_total, c.b_total));
+    const uint32_t kb = key_bytes_of(c.key_type);
+    const size_t total = c.a_total + c.b_total, words = c.num_segments + 1;
+    // an array of no elements is not looked at
+    if (!c.a_total) c.a_keys = nullptr, c.a_vals = nullptr;
+    if (!c.b_total) c.b_keys = nullptr, c.b_vals = nullptr;
+    if (!total) c.out_keys = nullptr, c.out_vals = nullptr;
+    if (c.a_total && !c.a_keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid a_keys buffer");
+    if (c.b_total && !c.b_keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid b_keys buffer");
+    if (total && !c.out_keys) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid out_keys buffer");
+    const bool with_vals = c.out_vals != nullptr;
+    if ((c.a_total && (c.a_vals != nullptr) != with_vals) || (c.b_total && (c.b_vals != nullptr) != with_vals))
+        return fail(GLU_ERROR_INVALID_ARGUMENT, "a_vals, b_vals and out_vals must be all NULL (keys only) or all non-NULL");
+    GLU_TRY(check_aligned(c.a_keys, kb, "a_keys", "the key size"));
+    GLU_TRY(check_aligned(c.b_keys, kb, "b_keys", "the key size"));
+    GLU_TRY(check_aligned(c.out_keys, kb, "out_keys", "the key size"));
+    GLU_TRY(check_aligned_4(c.a_vals, "a_vals"));
+    GLU_TRY(check_aligned_4(c.b_vals, "b_vals"));
+    GLU_TRY(check_aligned_4(c.out_vals, "out_vals"));
+    GLU_TRY(check_aligned_4(c.out_offsets, "out_offsets"));
+    GLU_TRY(check_disjoint({{c.out_keys, total * kb, "out_keys"}, {c.out_vals, total * 4, "out_vals"}, {c.out_offsets, words * 4, "out_offsets"}},
+                           {{c.a_keys, c.a_total * kb, "a_keys"},
+                            {c.b_keys, c.b_total * kb, "b_keys"},
+                            {c.a_vals, c.a_total * 4, "a_vals"},
+                            {c.b_vals, c.b_total * 4, "b_vals"},
+                            {c.a_offsets, words * 4, "a_offsets"},
+                            {c.b_offsets, words * 4, "b_offsets"}},
+                           kOutputsAfterInputs));
+
+    const MergePlan p = merge_batch_plan(total, c.num_segments, kb, with_vals);
+    merge->last = {p.tiles, p.kernels};
+    const hipStream_t st = pick_stream(c.stream);
+    if (!c.num_segments) // nothing to merge: out_offsets[0] = 0
+    {
+        if (c.out_offsets) HIP_TRY(hipMemsetAsync(c.out_offsets, 0, sizeof(uint32_t), st));
+        return GLU_OK;
+    }
+    GLU_TRY(merge->split.reserve(p.scratch_bytes));
+    return kb == 8 ? run_batch<uint64_t>(merge, c, p, st) : run_batch<uint32_t>(merge, c, p, st);
 }
 
 // ---- set operations
@@ -186,6 +282,60 @@ glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const uint32_t
     const hipStream_t st = pick_stream(stream);
     return kb == 8 ? run<uint64_t>(merge, a_keys, a_vals, a_count, b_keys, b_vals, b_count, out_keys, out_vals, (int) key_type, p, st)
                    : run<uint32_t>(merge, a_keys, a_vals, a_count, b_keys, b_vals, b_count, out_keys, out_vals, (int) key_type, p, st);
+}
+
+glu_status glu_merge_plan_batch(size_t total_count, size_t num_segments, glu_key_type key_type, int with_vals, uint32_t* tile, uint32_t* tiles,
+                                uint32_t* kernels, size_t* scratch_bytes)
+{
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_total(total_count, 0));
+    GLU_TRY(check_batch_segments(num_segments));
+    const MergePlan p = merge_batch_plan(total_count, num_segments, key_bytes_of((int) key_type), with_vals != 0);
+    store(tile, p.tile);
+    store(tiles, p.tiles);
+    store(kernels, p.kernels);
+    store(scratch_bytes, p.scratch_bytes);
+    return GLU_OK;
+}
+
+glu_status glu_merge_prepare_batch(glu_merge merge, size_t total_count, glu_key_type key_type)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(merge, "merge"));
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_total(total_count, 0));
+    // (the tile is the same with and without values; the boundaries do not depend on the number of segments)
+    return merge->split.reserve(merge_batch_plan(total_count, 1, key_bytes_of((int) key_type), true).scratch_bytes);
+}
+
+glu_status glu_merge_run_batch_offsets_ptr(glu_merge merge, const void* a_keys, const uint32_t* a_vals, const uint32_t* a_offsets, size_t a_total,
+                                           const void* b_keys, const uint32_t* b_vals, const uint32_t* b_offsets, size_t b_total,
+                                           size_t num_segments, void* out_keys, uint32_t* out_vals, uint32_t* out_offsets, glu_key_type key_type,
+                                           void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(merge, "merge"));
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_batch_segments(num_segments));
+    if (num_segments && (!a_offsets || !b_offsets)) return fail(GLU_ERROR_INVALID_ARGUMENT, "Invalid %s array", a_offsets ? "b_offsets" : "a_offsets");
+    GLU_TRY(check_aligned_4(a_offsets, "a_offsets"));
+    GLU_TRY(check_aligned_4(b_offsets, "b_offsets"));
+    if (!num_segments) a_offsets = b_offsets = nullptr; // (not looked at)
+    return merge_batch(merge, {a_keys, b_keys, a_vals, b_vals, a_offsets, b_offsets, 0, 0, a_total, b_total, num_segments, out_keys, out_vals,
+                               out_offsets, (int) key_type, stream});
+}
+
+glu_status glu_merge_run_batch_ptr(glu_merge merge, const void* a_keys, const uint32_t* a_vals, size_t a_len, const void* b_keys,
+                                   const uint32_t* b_vals, size_t b_len, size_t num_segments, void* out_keys, uint32_t* out_vals,
+                                   uint32_t* out_offsets, glu_key_type key_type, void* stream)
+{
+    GLU_TRY(enter());
+    GLU_TRY(check_not_null(merge, "merge"));
+    GLU_TRY(check_key_type((int) key_type));
+    GLU_TRY(check_batch_segments(num_segments));
+    GLU_TRY(check_total(a_len, b_len)); // (each below 2^32: the products below do not wrap)
+    return merge_batch(merge, {a_keys, b_keys, a_vals, b_vals, nullptr, nullptr, a_len, b_len, num_segments * a_len, num_segments * b_len,
+                               num_segments, out_keys, out_vals, out_offsets, (int) key_type, stream});
 }
 
 glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels)

@@ -147,6 +147,10 @@ SYMBOLS = [
     ("glu_merge_run_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
     ("glu_merge_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_merge_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_merge_prepare_batch", _int, [_vp, _sz, _int]),
+    ("glu_merge_run_batch_offsets_ptr", _int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _int, _vp]),
+    ("glu_merge_run_batch_ptr", _int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _int, _vp]),
+    ("glu_merge_plan_batch", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_set_ops_create", _int, [_P(_vp)]),
     ("glu_set_ops_destroy", _int, [_vp]),
     ("glu_set_ops_prepare", _int, [_vp, _sz, _int]),
@@ -441,6 +445,16 @@ def plan_merge(a_count, b_count, key_type="uint32", with_vals=True):
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_merge_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b),
                                ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def plan_merge_batch(total_count, num_segments, key_type="uint32", with_vals=True):
+    """(tile, tiles, kernels, scratch_bytes) of a batched merge of `total_count` = a_total + b_total keys in `num_segments` segments
+    (glu_merge_plan_batch; host only): merge's tile, ceil(total_count / tile), 2 kernels (1 for no keys, 0 for no segments), the bytes
+    of the boundary table."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_merge_plan_batch(total_count, num_segments, KEY_TYPES[key_type], 1 if with_vals else 0, ctypes.byref(a), ctypes.byref(b),
+                                     ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
 
 
@@ -908,8 +922,30 @@ class Merge(_Handle):
         check(lib().glu_merge_run_ptr(self._h, _vp(a_keys_ptr), _vp(a_vals_ptr), a_count, _vp(b_keys_ptr), _vp(b_vals_ptr), b_count,
                                       _vp(out_keys_ptr), _vp(out_vals_ptr), KEY_TYPES[key_type], _vp(stream)))
 
+    def prepare_batch(self, total_count, key_type="uint32"):
+        """Scratch for batched calls of up to `total_count` = a_total + b_total keys: they allocate nothing (capturable)
+        (glu_merge_prepare_batch)."""
+        check(lib().glu_merge_prepare_batch(self._h, total_count, KEY_TYPES[key_type]))
+
+    def run_batch_offsets_ptr(self, a_keys_ptr, a_vals_ptr, a_offsets_ptr, a_total, b_keys_ptr, b_vals_ptr, b_offsets_ptr, b_total,
+                              num_segments, out_keys_ptr, out_vals_ptr, out_offsets_ptr=None, key_type="uint32", stream=None):
+        """Segment s of the output = the merge of A[a_offsets[s], a_offsets[s + 1]) and B[b_offsets[s], b_offsets[s + 1]), the
+        segments back to back; the offsets are device arrays of num_segments + 1 uint32 words, a_total and b_total the arrays'
+        lengths.  out_offsets (optional) receives the num_segments + 1 output offsets (glu_merge_run_batch_offsets_ptr)."""
+        check(lib().glu_merge_run_batch_offsets_ptr(self._h, _vp(a_keys_ptr), _vp(a_vals_ptr), _vp(a_offsets_ptr), a_total, _vp(b_keys_ptr),
+                                                    _vp(b_vals_ptr), _vp(b_offsets_ptr), b_total, num_segments, _vp(out_keys_ptr),
+                                                    _vp(out_vals_ptr), _vp(out_offsets_ptr), KEY_TYPES[key_type], _vp(stream)))
+
+    def run_batch_ptr(self, a_keys_ptr, a_vals_ptr, a_len, b_keys_ptr, b_vals_ptr, b_len, num_segments, out_keys_ptr, out_vals_ptr,
+                      out_offsets_ptr=None, key_type="uint32", stream=None):
+        """The same over equal partitions: segment s is A[s * a_len, (s + 1) * a_len) and B[s * b_len, (s + 1) * b_len)
+        (glu_merge_run_batch_ptr)."""
+        check(lib().glu_merge_run_batch_ptr(self._h, _vp(a_keys_ptr), _vp(a_vals_ptr), a_len, _vp(b_keys_ptr), _vp(b_vals_ptr), b_len,
+                                            num_segments, _vp(out_keys_ptr), _vp(out_vals_ptr), _vp(out_offsets_ptr), KEY_TYPES[key_type],
+                                            _vp(stream)))
+
     def last(self):
-        """(tiles, kernels) of what the last run_ptr enqueued (glu_merge_last; no device read)."""
+        """(tiles, kernels) of what the last run_ptr or batched call enqueued (glu_merge_last; no device read)."""
         a, b = _u32(), _u32()
         check(lib().glu_merge_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value

@@ -914,8 +914,9 @@ GLU_API glu_status glu_sorted_search_plan_batch(size_t needle_total, glu_key_typ
  *     output overlapping an input or the other output.  A refused call writes nothing.
  *   - OUT OF SCOPE: more than two inputs (a merge tree is repeated calls); an in-place merge; values wider than 4 bytes (merge
  *     an iota as the values, and fetch the wide values through the merged iota with glu_gather_run_ptr, the gather by an
- *     arbitrary permutation; it takes one source array, so A's and B's values are copied into one array first); a
- *     segmented merge; counts that live on the device.  (Set operations on two sorted arrays: glu_set_ops_run_ptr below.) */
+ *     arbitrary permutation; it takes one source array, so A's and B's values are copied into one array first).  (A segmented
+ *     merge, and a merge whose counts live on the device: the batched calls below.  Set operations on two sorted arrays:
+ *     glu_set_ops_run_ptr below.) */
 typedef struct glu_merge_s* glu_merge;
 /* Not in the reference. */
 GLU_API glu_status glu_merge_create(glu_merge* out);
@@ -933,8 +934,56 @@ GLU_API glu_status glu_merge_run_ptr(glu_merge merge, const void* a_keys, const 
  * scratch_bytes = (tiles + 1) * 4 (0 if there is nothing to merge): what prepare reserves.  Any pointer may be NULL. */
 GLU_API glu_status glu_merge_plan(size_t a_count, size_t b_count, glu_key_type key_type, int with_vals, uint32_t* tile, uint32_t* tiles,
                                   uint32_t* kernels, size_t* scratch_bytes);
-/* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
+/* Not in the reference.  What the host enqueued in the object's last run_ptr or batched call (no device read): the tiles and the
+ * kernels. */
 GLU_API glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* kernels);
+
+/* ---- batched merge (not in the reference): the two sorted runs of every segment into one, all segments in one call.
+ *   - a_offsets and b_offsets are DEVICE arrays of num_segments + 1 uint32_t words; the host never reads them.  Segment s of A is
+ *     A[a_offsets[s], a_offsets[s + 1]), of B likewise.  a_total and b_total are the host-known lengths of the arrays (they may be
+ *     larger than the last offsets): they bound every access and size the grids.  With oa[s] = a_offsets[s] - a_offsets[0] and
+ *     ob[s] likewise, the output of segment s is out[oa[s] + ob[s] .. oa[s + 1] + ob[s + 1]) and holds what glu_merge_run_ptr
+ *     writes for that segment's two runs: the output is the stable sort of all elements by (segment, enc(key), side), A first.
+ *     All six glu_key_type's; values uint32_t, all three value pointers given or all NULL; keys copied bit for bit.
+ *   - Entries of out_keys / out_vals at and behind oa[S] + ob[S] are not touched.  out_offsets is optional: when given, all its
+ *     num_segments + 1 entries oa[s] + ob[s] are written -- the form every batched call takes, so the merged rows go straight
+ *     into a batched top-k, reduce or a further batched merge.  A segment empty on one side or on both is legal, anywhere and
+ *     in any number.  num_segments == 0 merges nothing and writes out_offsets[0] = 0.
+ *   - num_segments == 1 with offsets {0, n_a} and {0, n_b} written by the device is the merge whose COUNTS LIVE ON THE DEVICE
+ *     (the num_out of select, the set operations, key runs, top-k): no host read, capturable.
+ *   - a_total + b_total <= 2^32 - 1; num_segments <= 2^24.  Every array at any multiple of its element size.  The outputs
+ *     (out_keys and out_vals over a_total + b_total elements, out_offsets) overlap no input, no offsets array and not each other.
+ *   - NOT TRUSTED: inputs that are not sorted inside a segment, offsets that decrease or exceed their total give unspecified
+ *     CONTENTS.  Nothing outside [0, a_total), [0, b_total), out[0, a_total + b_total) and the num_segments + 1 offset words is
+ *     read or written, no output is written twice, and every out_offsets entry written is at most a_total + b_total (every offset
+ *     is pinned into its side before use; tests/test_merge_batch_path.py walks the arithmetic on the host).
+ *   - One merge path over all of A and B in the order (segment, enc(key)): a partition kernel (one thread per tile boundary:
+ *     the boundary's segment by a bound over the offsets, then the split inside that segment; it also writes out_offsets) and a
+ *     tile kernel (one workgroup per tile of the single call's size; a tile inside one segment runs the single merge's body, a
+ *     tile over several segments merges by (segment, key) with a segment word beside every staged key).  Balanced over the
+ *     outputs: one long segment fills the device, empty segments cost no tile anything.  No atomics, no look-back, no host
+ *     synchronisation; the same call gives the same bits; after glu_merge_prepare_batch no allocation, and one captured call
+ *     replays on other keys AND other offsets of the same capacity (the grids follow from a_total, b_total, num_segments).
+ *   - GLU_ERROR_INVALID_ARGUMENT as for the single call, and for num_segments > 2^24 or a NULL offsets array.
+ *   - OUT OF SCOPE: pairs of adjacent segments of one array; more than two inputs; batched set operations; values wider than 4
+ *     bytes; a key type per segment; 64-bit offsets; an in-place merge. */
+/* Not in the reference.  Grow-only scratch for batched calls with a_total + b_total <= total_count keys of `key_type`. */
+GLU_API glu_status glu_merge_prepare_batch(glu_merge merge, size_t total_count, glu_key_type key_type);
+/* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_merge_run_batch_offsets_ptr(glu_merge merge, const void* a_keys, const uint32_t* a_vals, const uint32_t* a_offsets,
+                                                   size_t a_total, const void* b_keys, const uint32_t* b_vals, const uint32_t* b_offsets,
+                                                   size_t b_total, size_t num_segments, void* out_keys, uint32_t* out_vals,
+                                                   uint32_t* out_offsets, glu_key_type key_type, void* stream);
+/* Not in the reference.  Equal partitions: a_offsets[s] = s * a_len, b_offsets[s] = s * b_len (a_total = num_segments * a_len,
+ * b_total likewise); either length may be 0. */
+GLU_API glu_status glu_merge_run_batch_ptr(glu_merge merge, const void* a_keys, const uint32_t* a_vals, size_t a_len, const void* b_keys,
+                                           const uint32_t* b_vals, size_t b_len, size_t num_segments, void* out_keys, uint32_t* out_vals,
+                                           uint32_t* out_offsets, glu_key_type key_type, void* stream);
+/* Not in the reference.  Host only, no device, pure: tile as glu_merge_plan, tiles = ceil(total_count / tile) with total_count =
+ * a_total + b_total, kernels = 2 (1 where total_count is 0: the partition kernel writes out_offsets; 0 where num_segments is 0),
+ * scratch_bytes = (tiles + 1) * 8: what prepare_batch reserves.  Any pointer may be NULL. */
+GLU_API glu_status glu_merge_plan_batch(size_t total_count, size_t num_segments, glu_key_type key_type, int with_vals, uint32_t* tile,
+                                        uint32_t* tiles, uint32_t* kernels, size_t* scratch_bytes);
 
 /* ---- set operations (not in the reference): union, intersection, difference and symmetric difference of two sorted arrays of
  * keys, with or without 4-byte values, on the device and on the caller's stream: std::set_union / set_intersection /
