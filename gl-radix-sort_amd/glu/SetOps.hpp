@@ -76,6 +76,44 @@ namespace glu
                     device_out_keys, device_out_vals, max_out, device_num_out, key_type, stream);
         }
 
+        /// Scratch for batched calls of up to `total_count` = a_total + b_total keys in up to `num_segments` segments: they then
+        /// allocate nothing and can be captured.
+        void prepare_batch(size_t total_count, size_t num_segments = 1, glu_key_type key_type = GLU_KEY_UINT32)
+        {
+            GLU_CHECK_STATUS(glu_set_ops_prepare_batch(m_impl, total_count, num_segments, key_type));
+        }
+
+        /// Any of the four operations on every segment's two sorted runs in one call: segment s of the result is `op` of
+        /// A[a_offsets[s], a_offsets[s + 1]) and B[b_offsets[s], b_offsets[s + 1]), the segments' results back to back from out[0].
+        /// The offsets are DEVICE arrays of num_segments + 1 words; a_total and b_total are the arrays' lengths.  Keys never match
+        /// across segments.  *device_num_out receives the total kept, also beyond max_out; device_out_offsets (optional) the
+        /// num_segments + 1 offsets of the compacted segments, held to max_out (in a call that only counts: the running
+        /// cardinalities, not held to it).  One segment whose offset words were written on the device is the set operation whose
+        /// counts live on the device (glu_set_ops_run_batch_offsets_ptr in glu_hip.h).
+        void set_op_batch_offsets(glu_set_op op, const void* device_a_keys, const uint32_t* device_a_vals, const uint32_t* device_a_offsets,
+                                  size_t a_total, const void* device_b_keys, const uint32_t* device_b_vals, const uint32_t* device_b_offsets,
+                                  size_t b_total, size_t num_segments, void* device_out_keys, uint32_t* device_out_vals, size_t max_out,
+                                  uint32_t* device_num_out, uint32_t* device_out_offsets = nullptr, glu_key_type key_type = GLU_KEY_UINT32,
+                                  void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_set_ops_run_batch_offsets_ptr(m_impl, (int) op, device_a_keys, device_a_vals, device_a_offsets, a_total,
+                                                               device_b_keys, device_b_vals, device_b_offsets, b_total, num_segments,
+                                                               device_out_keys, device_out_vals, max_out, device_out_offsets, device_num_out,
+                                                               key_type, stream));
+        }
+
+        /// The same over equal partitions: segment s is A[s * a_len, (s + 1) * a_len) and B[s * b_len, (s + 1) * b_len); either
+        /// length may be 0.
+        void set_op_batch(glu_set_op op, const void* device_a_keys, const uint32_t* device_a_vals, size_t a_len, const void* device_b_keys,
+                          const uint32_t* device_b_vals, size_t b_len, size_t num_segments, void* device_out_keys, uint32_t* device_out_vals,
+                          size_t max_out, uint32_t* device_num_out, uint32_t* device_out_offsets = nullptr,
+                          glu_key_type key_type = GLU_KEY_UINT32, void* stream = nullptr)
+        {
+            GLU_CHECK_STATUS(glu_set_ops_run_batch_ptr(m_impl, (int) op, device_a_keys, device_a_vals, a_len, device_b_keys, device_b_vals, b_len,
+                                                       num_segments, device_out_keys, device_out_vals, max_out, device_out_offsets,
+                                                       device_num_out, key_type, stream));
+        }
+
         /// What a call with these counts does (glu_set_ops_plan; host only, no device needed).  with_arrays: the call writes its
         /// result (false: it only counts).
         struct Plan
@@ -87,6 +125,17 @@ namespace glu
         {
             Plan p;
             GLU_CHECK_STATUS(glu_set_ops_plan(a_count, b_count, key_type, with_arrays ? 1 : 0, &p.tile, &p.tiles, &p.kernels, &p.scratch_bytes));
+            return p;
+        }
+
+        /// What a batched call does (glu_set_ops_plan_batch; host only, no device needed).  with_arrays: the call writes its result;
+        /// with_offsets: it writes out_offsets.
+        [[nodiscard]] static Plan plan_batch(size_t a_total, size_t b_total, size_t num_segments, glu_key_type key_type = GLU_KEY_UINT32,
+                                             bool with_arrays = true, bool with_offsets = true)
+        {
+            Plan p;
+            GLU_CHECK_STATUS(glu_set_ops_plan_batch(a_total, b_total, num_segments, key_type, with_arrays ? 1 : 0, with_offsets ? 1 : 0, &p.tile,
+                                                    &p.tiles, &p.kernels, &p.scratch_bytes));
             return p;
         }
 

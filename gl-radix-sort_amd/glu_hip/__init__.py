@@ -157,6 +157,10 @@ SYMBOLS = [
     ("glu_set_ops_run_ptr", _int, [_vp, _int, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _int, _vp]),
     ("glu_set_ops_plan", _int, [_sz, _sz, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_set_ops_last", _int, [_vp, _P(_u32), _P(_u32)]),
+    ("glu_set_ops_prepare_batch", _int, [_vp, _sz, _sz, _int]),
+    ("glu_set_ops_run_batch_offsets_ptr", _int, [_vp, _int, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
+    ("glu_set_ops_run_batch_ptr", _int, [_vp, _int, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp, _int, _vp]),
+    ("glu_set_ops_plan_batch", _int, [_sz, _sz, _sz, _int, _int, _int, _P(_u32), _P(_u32), _P(_u32), _P(_sz)]),
     ("glu_histogram_create", _int, [_P(_vp)]),
     ("glu_histogram_destroy", _int, [_vp]),
     ("glu_histogram_prepare", _int, [_vp, _sz, _sz]),
@@ -470,6 +474,16 @@ def plan_set_ops(a_count, b_count, key_type="uint32", with_arrays=True):
     a, b, c, d = _u32(), _u32(), _u32(), _sz()
     check(lib().glu_set_ops_plan(a_count, b_count, KEY_TYPES[key_type], 1 if with_arrays else 0, ctypes.byref(a), ctypes.byref(b),
                                  ctypes.byref(c), ctypes.byref(d)))
+    return a.value, b.value, c.value, d.value
+
+
+def plan_set_ops_batch(a_total, b_total, num_segments, key_type="uint32", with_arrays=True, with_offsets=True):
+    """(tile, tiles, kernels, scratch_bytes) of a batched set operation on `a_total` and `b_total` keys in `num_segments` segments
+    (glu_set_ops_plan_batch; host only): merge's tile, ceil((a_total + b_total) / tile), 3 kernels + 1 with out_offsets + 1 with
+    arrays (1 + with_offsets for no keys, 1 for no segments), the bytes of the bounds, the tile counts and the threads' words."""
+    a, b, c, d = _u32(), _u32(), _u32(), _sz()
+    check(lib().glu_set_ops_plan_batch(a_total, b_total, num_segments, KEY_TYPES[key_type], 1 if with_arrays else 0,
+                                       1 if with_offsets else 0, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
     return a.value, b.value, c.value, d.value
 
 
@@ -974,8 +988,33 @@ class SetOps(_Handle):
                                         _vp(b_vals_ptr), b_count, _vp(out_keys_ptr), _vp(out_vals_ptr), max_out, _vp(num_out_ptr),
                                         KEY_TYPES[key_type], _vp(stream)))
 
+    def prepare_batch(self, total_count, num_segments=1, key_type="uint32"):
+        """Scratch for batched calls of up to `total_count` = a_total + b_total keys: they allocate nothing (capturable)
+        (glu_set_ops_prepare_batch)."""
+        check(lib().glu_set_ops_prepare_batch(self._h, total_count, num_segments, KEY_TYPES[key_type]))
+
+    def run_batch_offsets_ptr(self, op, a_keys_ptr, a_vals_ptr, a_offsets_ptr, a_total, b_keys_ptr, b_vals_ptr, b_offsets_ptr, b_total,
+                              num_segments, out_keys_ptr, out_vals_ptr, max_out, num_out_ptr, out_offsets_ptr=None, key_type="uint32",
+                              stream=None):
+        """Segment s of the result = `op` of A[a_offsets[s], a_offsets[s + 1]) and B[b_offsets[s], b_offsets[s + 1]), the segments'
+        results back to back; the offsets are device arrays of num_segments + 1 uint32 words, a_total and b_total the arrays' lengths.
+        *num_out receives the total kept; out_offsets (optional) the num_segments + 1 offsets of the compacted segments, held to
+        max_out (not in a call that only counts) (glu_set_ops_run_batch_offsets_ptr)."""
+        check(lib().glu_set_ops_run_batch_offsets_ptr(self._h, SET_OPS.get(op, op), _vp(a_keys_ptr), _vp(a_vals_ptr), _vp(a_offsets_ptr),
+                                                      a_total, _vp(b_keys_ptr), _vp(b_vals_ptr), _vp(b_offsets_ptr), b_total, num_segments,
+                                                      _vp(out_keys_ptr), _vp(out_vals_ptr), max_out, _vp(out_offsets_ptr), _vp(num_out_ptr),
+                                                      KEY_TYPES[key_type], _vp(stream)))
+
+    def run_batch_ptr(self, op, a_keys_ptr, a_vals_ptr, a_len, b_keys_ptr, b_vals_ptr, b_len, num_segments, out_keys_ptr, out_vals_ptr,
+                      max_out, num_out_ptr, out_offsets_ptr=None, key_type="uint32", stream=None):
+        """The same over equal partitions: segment s is A[s * a_len, (s + 1) * a_len) and B[s * b_len, (s + 1) * b_len)
+        (glu_set_ops_run_batch_ptr)."""
+        check(lib().glu_set_ops_run_batch_ptr(self._h, SET_OPS.get(op, op), _vp(a_keys_ptr), _vp(a_vals_ptr), a_len, _vp(b_keys_ptr),
+                                              _vp(b_vals_ptr), b_len, num_segments, _vp(out_keys_ptr), _vp(out_vals_ptr), max_out,
+                                              _vp(out_offsets_ptr), _vp(num_out_ptr), KEY_TYPES[key_type], _vp(stream)))
+
     def last(self):
-        """(tiles, kernels) of what the last run_ptr enqueued (glu_set_ops_last; no device read)."""
+        """(tiles, kernels) of what the last run_ptr or batched call enqueued (glu_set_ops_last; no device read)."""
         a, b = _u32(), _u32()
         check(lib().glu_set_ops_last(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value

@@ -965,8 +965,8 @@ GLU_API glu_status glu_merge_last(glu_merge merge, uint32_t* tiles, uint32_t* ke
  *     synchronisation; the same call gives the same bits; after glu_merge_prepare_batch no allocation, and one captured call
  *     replays on other keys AND other offsets of the same capacity (the grids follow from a_total, b_total, num_segments).
  *   - GLU_ERROR_INVALID_ARGUMENT as for the single call, and for num_segments > 2^24 or a NULL offsets array.
- *   - OUT OF SCOPE: pairs of adjacent segments of one array; more than two inputs; batched set operations; values wider than 4
- *     bytes; a key type per segment; 64-bit offsets; an in-place merge. */
+ *   - OUT OF SCOPE: pairs of adjacent segments of one array; more than two inputs; values wider than 4 bytes; a key type per
+ *     segment; 64-bit offsets; an in-place merge.  (Batched set operations: glu_set_ops_run_batch_offsets_ptr below.) */
 /* Not in the reference.  Grow-only scratch for batched calls with a_total + b_total <= total_count keys of `key_type`. */
 GLU_API glu_status glu_merge_prepare_batch(glu_merge merge, size_t total_count, glu_key_type key_type);
 /* Not in the reference.  The contract above.  Enqueues on `stream` (NULL: the library's queue) and returns. */
@@ -1026,8 +1026,8 @@ GLU_API glu_status glu_merge_plan_batch(size_t total_count, size_t num_segments,
  *     a call that only counts; an op or a key type outside its list; misalignment; the limits above; an output overlapping an
  *     input, another output or num_out.  A refused call writes nothing.
  *   - OUT OF SCOPE: more than two inputs; set semantics that drop duplicates within one input (run glu_key_runs_run_ptr first: its
- *     unique keys are a set); values wider than 4 bytes (carry an iota and gather, as for merge); the indices of the partners in B;
- *     counts that live on the device. */
+ *     unique keys are a set); values wider than 4 bytes (carry an iota and gather, as for merge); the indices of the partners in B.
+ *     (Counts that live on the device: the batched call below with num_segments == 1.) */
 typedef enum
 {
     GLU_SET_UNION = 0,
@@ -1054,8 +1054,77 @@ GLU_API glu_status glu_set_ops_run_ptr(glu_set_ops set_ops, int op, const void* 
  * prepare reserves.  Any pointer may be NULL. */
 GLU_API glu_status glu_set_ops_plan(size_t a_count, size_t b_count, glu_key_type key_type, int with_arrays, uint32_t* tile,
                                     uint32_t* tiles, uint32_t* kernels, size_t* scratch_bytes);
-/* Not in the reference.  What the host enqueued in the object's last run_ptr (no device read): the tiles and the kernels. */
+/* Not in the reference.  What the host enqueued in the object's last run_ptr or batched call (no device read): the tiles and the
+ * kernels. */
 GLU_API glu_status glu_set_ops_last(glu_set_ops set_ops, uint32_t* tiles, uint32_t* kernels);
+
+/* ---- batched set operations (not in the reference): the set operation of the two sorted runs of every segment, all segments in
+ * one call.  The contract is the batched merge's for the segments and the single set operation's for the result.
+ *   - SEGMENTS.  a_offsets and b_offsets are DEVICE arrays of num_segments + 1 uint32_t words; the host never reads them.  Segment s
+ *     of A is A[a_offsets[s], a_offsets[s + 1]), of B likewise.  a_total and b_total are the host-known lengths of the arrays (they
+ *     may be larger than the last offsets): they bound every access and size every grid.  Every offset is pinned into its side
+ *     before use, exactly as the batched merge pins it.  num_segments <= 2^24; a_total + b_total <= 2^32 - 1; max_out < 2^32.
+ *   - RESULT.  Segment s of the result is what glu_set_ops_run_ptr(op, A_s, B_s) writes: the same multiset semantics, all six
+ *     glu_key_type's, equality on bits, A first among equal keys, the intersection holding A's keys and values.  The segments'
+ *     results lie back to back from out[0], in segment order.  Keys NEVER MATCH ACROSS SEGMENTS: a key that ends A_s and begins
+ *     B_{s + 1} is two different elements.  b_vals is read only for the union and the symmetric difference (with values, b_total
+ *     > 0: required there, ignored otherwise); a_vals and out_vals are both NULL or both non-NULL when a_total > 0.
+ *   - *num_out (uint32_t, on the device, required) receives the true total S of kept elements, also beyond max_out.
+ *     out[0 .. min(S, max_out)) is written; nothing behind it is touched.  out_keys NULL or max_out 0 ONLY COUNTS; out_vals must
+ *     then be NULL.
+ *   - out_offsets is optional.  When given, all its num_segments + 1 entries are written: entry s = min(max_out, the kept elements
+ *     of the segments < s) -- the batched select's clamp: the entries describe what was written, and the next batched call over
+ *     them stays in bounds.  An emptied segment stays an empty segment.  In a call that ONLY COUNTS the entries are NOT clamped by
+ *     max_out (there is no array to stay inside): they are the running sums of the per-segment cardinalities, held to the bound
+ *     below alone.
+ *   - num_segments == 0 writes *num_out = 0 and out_offsets[0] = 0.  num_segments == 1 with both pairs of offset words written on
+ *     the device ({0, n_a} and {0, n_b}, n_a being the num_out of an earlier call) is the set operation whose COUNTS LIVE ON THE
+ *     DEVICE: a chain of set operations without a host read.
+ *   - BOUND.  bound = the most outputs of the operation over the host-known totals: a_total + b_total for union and symmetric
+ *     difference, a_total for difference, min(a_total, b_total) for intersection.  The first min(bound, max_out) entries of out_keys
+ *     and out_vals, the num_segments + 1 entries of out_offsets and num_out must overlap no input, no offsets array and not each
+ *     other.  Every array at any multiple of its element size.  The inputs and the offsets are READ ONLY.
+ *   - Five kernels at most, on the caller's stream alone: the bounds of every tile boundary (the batched merge's segment and split,
+ *     and where the first key's copies start inside that segment: 16 bytes a boundary), the kept elements of every tile decided and
+ *     counted in LDS (each thread leaves one word: its decisions as bits and its rank in the tile), the counts scanned (*num_out),
+ *     one thread per out_offsets entry (where given), and the kept elements of every tile written at their ranks (where something
+ *     can be written; it takes the count kernel's decisions and does not decide twice).  No atomics, no side stream, no host
+ *     synchronisation, nothing in arrival order: the same bits every time.  After glu_set_ops_prepare_batch no allocation, and one
+ *     captured call (one stream, no parallel branches) replays on other keys AND other offsets of the same capacity.
+ *   - NOT TRUSTED: runs that are not sorted, offsets that decrease or exceed their totals give unspecified CONTENTS; still *num_out
+ *     <= bound, every out_offsets entry <= min(bound, max_out) (<= bound in a call that only counts), never an access outside the
+ *     arrays and never a write at or behind out[min(bound, max_out)] (tests/test_set_ops_batch_path.py walks the arithmetic on the
+ *     host).
+ *   - GLU_ERROR_INVALID_ARGUMENT as for glu_set_ops_run_ptr and the batched merge, each with a message that names the argument:
+ *     NULL set_ops; a NULL key pointer of a side with elements; NULL num_out; a_vals without out_vals or the reverse; a required
+ *     b_vals missing; out_vals in a call that only counts; an op or a key type outside its list; misalignment; the limits above;
+ *     num_segments > 2^24; a NULL offsets array; an output overlapping an input, an offsets array or another output.  A refused
+ *     call writes nothing.
+ *   - OUT OF SCOPE: more than two inputs; values wider than 4 bytes; a key type or an operation per segment; 64-bit offsets; the
+ *     indices of the partners in B. */
+/* Not in the reference.  Grow-only scratch for batched calls with a_total + b_total <= total_count keys of `key_type` in up to
+ * num_segments segments, with or without arrays and out_offsets: after it a batched call allocates nothing. */
+GLU_API glu_status glu_set_ops_prepare_batch(glu_set_ops set_ops, size_t total_count, size_t num_segments, glu_key_type key_type);
+/* Not in the reference.  The contract above; `op` is a glu_set_op.  Enqueues on `stream` (NULL: the library's queue) and returns. */
+GLU_API glu_status glu_set_ops_run_batch_offsets_ptr(glu_set_ops set_ops, int op, const void* a_keys, const uint32_t* a_vals,
+                                                     const uint32_t* a_offsets, size_t a_total, const void* b_keys, const uint32_t* b_vals,
+                                                     const uint32_t* b_offsets, size_t b_total, size_t num_segments, void* out_keys,
+                                                     uint32_t* out_vals, size_t max_out, uint32_t* out_offsets, uint32_t* num_out,
+                                                     glu_key_type key_type, void* stream);
+/* Not in the reference.  Equal partitions: a_offsets[s] = s * a_len, b_offsets[s] = s * b_len (a_total = num_segments * a_len,
+ * b_total likewise); either length may be 0. */
+GLU_API glu_status glu_set_ops_run_batch_ptr(glu_set_ops set_ops, int op, const void* a_keys, const uint32_t* a_vals, size_t a_len,
+                                             const void* b_keys, const uint32_t* b_vals, size_t b_len, size_t num_segments, void* out_keys,
+                                             uint32_t* out_vals, size_t max_out, uint32_t* out_offsets, uint32_t* num_out,
+                                             glu_key_type key_type, void* stream);
+/* Not in the reference.  Host only, no device, pure: tile as glu_set_ops_plan, tiles = ceil((a_total + b_total) / tile); kernels = 3
+ * (bounds, count, scan) + 1 with_offsets (out_offsets given) + 1 with_arrays (out_keys given and max_out > 0); with no keys
+ * 1 + with_offsets (the scan writes *num_out = 0, the offsets kernel its zeros); with no segments 1 (the scan).  scratch_bytes =
+ * (tiles + 1) * 16 + tiles * 4, and tiles * 1024 more (one word per thread and tile: the count kernel's decisions, read by the
+ * offsets and the write kernel) unless the call only counts without out_offsets; 0 with no keys.  What prepare_batch reserves is
+ * the plan with arrays and offsets.  Any pointer may be NULL. */
+GLU_API glu_status glu_set_ops_plan_batch(size_t a_total, size_t b_total, size_t num_segments, glu_key_type key_type, int with_arrays,
+                                          int with_offsets, uint32_t* tile, uint32_t* tiles, uint32_t* kernels, size_t* scratch_bytes);
 
 /* ---- histogram (not in the reference): how many samples fall into each bin, over even bins (numpy.histogram with a range,
  * torch.histc, torch.bincount) or over sorted bin edges (numpy.histogram with edges), on the device and on the caller's stream.
