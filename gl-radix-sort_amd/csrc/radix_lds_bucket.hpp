@@ -21,10 +21,14 @@
 //       1. bucket = the word's top DIGIT_BITS bits (about as many buckets as the tile has slots: uniformly drawn keys leave 1 .. 1.5
 //          words per bucket); a returning LDS atomic counts the bucket and hands the word a place in it;
 //       2. one scan over the buckets; the words go to bucket start + place;
-//       3. every bucket with more than one word is put in order by the thread that owns it: up to four (eight) words into
-//          registers, a sorting network of min / max, back.  Exact, because words are unique.  (Round 6's first form let every
-//          word count the smaller words of its bucket in a loop: a chain of dependent LDS reads as long as the longest bucket
-//          any lane of the wave met -- slower than the ballots, profiles/r06/finish_bucket_first.txt.)
+//       3. every bucket with more than one word is put in order by the thread that owns it (bucket_order.hpp, plain C++ that the
+//          host tests too): up to four (eight) words into registers, a sorting network of min / max, back.  Exact, because words
+//          are unique.  A lane visits only its buckets of two words or more, through a bit mask of its BPT table entries, and the
+//          rare buckets of five or more wait in a second mask for a loop of their own: a wave makes as many trips as its busiest
+//          lane has such buckets (about 9 of 16 for uniformly drawn keys) instead of BPT, and the 8-word network leaves the common
+//          loop.  Step 3 was 0.16 ms of the kernel's 0.87 at 2^28 pairs and is 0.06 of 0.77 (profiles/r08/).  (Round 6's first form
+//          let every word count the smaller words of its bucket in a loop: a chain of dependent LDS reads as long as the longest
+//          bucket any lane of the wave met -- slower than the ballots, profiles/r06/finish_bucket_first.txt.)
 //     67 vector instructions per pair instead of 130 (SQ_INSTS_VALU, profiles/r06/finish_bucket_what_bounds_it.txt).
 //   * CROWDED RUNS.  Keys whose low bits repeat (a run of a few distinct keys, keys that are multiples of 65536) fill few
 //     buckets with many words, and step 3 is made for buckets of a few.  A word that finds kBucketMaxLen others in its bucket
@@ -36,7 +40,8 @@
 //     uncrowded path 9 % in registers and scalar spills, profiles/r06/finish_bucket_variants.txt.)
 //   * OUTPUT.  Lane j reads four consecutive ordered words (one 16-byte LDS load; the word positions are shifted by
 //     front & 3 so that this is aligned on both sides), rebuilds the keys (run's upper bits | field), gathers the four values
-//     by slot, and stores 16 bytes of keys and 16 of values, non-temporal.
+//     by slot, and stores 16 bytes of keys and 16 of values, non-temporal.  In the two ragged pieces at the run's ends a position
+//     outside the run holds no word: nothing is rebuilt or gathered from it (what stands there as a slot may lie past vstage).
 //
 //   * NARROW HAND-OFF (PassPlan::narrow; untyped 4-byte keys with values).  Behind the two top-bit passes a pair's position says what
 //     its top key bits are, so the second scatter may have left only the low 16 bits of every key, in a side array of 2-byte keys
@@ -48,6 +53,7 @@
 // PassPlan as before.  Runs longer than the tile are left to the segmented passes (long_ok) exactly as before.
 #pragma once
 
+#include "bucket_order.hpp"
 #include "radix_lds_finish.hpp"
 
 namespace glu_hip
@@ -65,9 +71,6 @@ constexpr uint32_t bucket_floor_pow2(uint32_t v)
     return p;
 }
 
-// a bucket longer than this makes the run a crowded one (step 3 sorts buckets in registers, networks for 4 and 8 words, and by
-// insertion in the stage beyond: quadratic, one lane at work)
-constexpr uint32_t kBucketMaxLen = 24;
 // The value loads are issued behind the scatter of the words instead of with the key loads: 20 registers fewer while the words
 // are ranked, and a crowded run never loads its values here.  4-byte keys 0.89 -> 0.81 ms at 2^28 pairs; 8-byte keys 1.41 -> 1.45
 // (profiles/r06/finish_bucket_variants.txt), so by key size.  -DGLU_BUCKET_LATE_VALUES=0 / 1: tuning builds.
@@ -421,67 +424,12 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
         __syncthreads();
         if (VALS && kBucketLateValues) load_values(); // (their latency passes under step 3)
         // ---- 3. buckets with more than one word, by the thread that owns them (bucket j * THREADS + tid: neighbouring lanes work on
-        // neighbouring stretches of the stage): up to 4 (8) words into registers, pads ~0 behind them, a sorting network, back
-        uint32_t hm_next = s.a.hist[tid];
-#pragma unroll 1
-        for (int j = 0; j < BPT; j++)
-        {
-            const uint32_t hm = hm_next;
-            if (j + 1 < BPT) hm_next = s.a.hist[(j + 1) * THREADS + tid];
-            const uint32_t st = hm & 0xFFFFu, m = hm >> 16;
-            if (m >= 2u)
-            {
-                auto cx = [](WordT& a, WordT& b) {
-                    const WordT lo = a < b ? a : b, hi = a < b ? b : a;
-                    a = lo, b = hi;
-                };
-                if (m <= 4u)
-                {
-                    WordT x0 = s.wstage[st], x1 = s.wstage[st + 1], x2 = s.wstage[st + 2], x3 = s.wstage[st + 3];
-                    x2 = m > 2u ? x2 : INVALID;
-                    x3 = m > 3u ? x3 : INVALID;
-                    cx(x0, x1), cx(x2, x3), cx(x0, x2), cx(x1, x3), cx(x1, x2);
-                    s.wstage[st] = x0, s.wstage[st + 1] = x1;
-                    if (m > 2u) s.wstage[st + 2] = x2;
-                    if (m > 3u) s.wstage[st + 3] = x3;
-                }
-                else if (m <= 8u)
-                {
-                    WordT x[8];
-#pragma unroll
-                    for (int e = 0; e < 8; e++) x[e] = s.wstage[st + e];
-#pragma unroll
-                    for (int e = 5; e < 8; e++) x[e] = m > (uint32_t) e ? x[e] : INVALID;
-                    // (odd-even merge sort of 8: 19 exchanges)
-                    cx(x[0], x[1]), cx(x[2], x[3]), cx(x[4], x[5]), cx(x[6], x[7]);
-                    cx(x[0], x[2]), cx(x[1], x[3]), cx(x[4], x[6]), cx(x[5], x[7]);
-                    cx(x[1], x[2]), cx(x[5], x[6]);
-                    cx(x[0], x[4]), cx(x[1], x[5]), cx(x[2], x[6]), cx(x[3], x[7]);
-                    cx(x[2], x[4]), cx(x[3], x[5]);
-                    cx(x[1], x[2]), cx(x[3], x[4]), cx(x[5], x[6]);
-#pragma unroll
-                    for (int e = 0; e < 8; e++)
-                        if (m > (uint32_t) e) s.wstage[st + e] = x[e];
-                }
-                else
-                {
-                    // (9 .. kBucketMaxLen words: one bucket in 10^6 for uniformly drawn keys -- stable insertion in the stage)
-                    for (uint32_t a = st + 1u; a < st + m; a++)
-                    {
-                        const WordT x = s.wstage[a];
-                        uint32_t b = a;
-                        while (b > st)
-                        {
-                            const WordT y = s.wstage[b - 1u];
-                            if (y < x) break;
-                            s.wstage[b] = y;
-                            b--;
-                        }
-                        s.wstage[b] = x;
-                    }
-                }
-            }
-        }
+        // neighbouring stretches of the stage): each lane walks only its buckets of two words or more -- bucket_order.hpp: two bit
+        // masks per lane, up to 4 (8) words into registers, pads ~0 behind them, a sorting network, back.  (The 4-word body reads four
+        // places whatever the bucket holds: up to two words past a bucket of two, which lie inside wstage -- CAP + 12 words, the
+        // buckets end at f4 + len <= TILE + 3 -- and belong to neighbouring buckets, maybe being written by their lanes at this moment.
+        // They are replaced by the pad before use and never written back: see bucket_order4.)
+        bucket_order_walk<BPT>(&s.wstage[0], [&](int j) { return s.a.hist[(uint32_t) j * THREADS + tid]; });
         if (VALS)
         {
             __syncthreads(); // (the bucket table has been read)
@@ -509,17 +457,17 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
                 w4[0] = (WordT) v0.x | ((WordT) v0.y << 32), w4[1] = (WordT) v0.z | ((WordT) v0.w << 32);
                 w4[2] = (WordT) v1.x | ((WordT) v1.y << 32), w4[3] = (WordT) v1.z | ((WordT) v1.w << 32);
             }
-            KeyT k4[4];
-            uint32_t v4[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-            {
-                k4[e] = codec_out.decode((KeyT) (run_hi | (KeyT) ((w4[e] >> SB) & low_mask)));
-                v4[e] = VALS ? s.a.vstage[(uint32_t) w4[e] & SMASK] : 0u;
-            }
+            // (a word is rebuilt into its key, and its value gathered by its slot, only where the position lies in the run: the stage
+            // holds nothing in front of f4 and behind f4 + len, and what stands there as a slot may lie past vstage)
+            auto key_of = [&](WordT w) { return codec_out.decode((KeyT) (run_hi | (KeyT) ((w >> SB) & low_mask))); };
+            auto value_of = [&](WordT w) { return VALS ? s.a.vstage[(uint32_t) w & SMASK] : 0u; };
             const uint32_t p0 = j * 4u; // shifted position of the piece's first element; the run's are [f4, f4 + len)
             if (p0 >= f4 && p0 + 4u <= f4 + len)
             {
+                KeyT k4[4];
+                uint32_t v4[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) k4[e] = key_of(w4[e]), v4[e] = value_of(w4[e]);
                 if constexpr (sizeof(KeyT) == 4)
                 {
                     const u32x4_t kv = {(uint32_t) k4[0], (uint32_t) k4[1], (uint32_t) k4[2], (uint32_t) k4[3]};
@@ -546,8 +494,8 @@ __global__ __launch_bounds__(THREADS, GLU_BUCKET_WAVES_PER_SIMD) void radix_fini
                     const uint32_t p = p0 + e;
                     if (p >= f4 && p < f4 + len)
                     {
-                        __builtin_nontemporal_store(k4[e], &keys[ebase + p]);
-                        if (VALS) __builtin_nontemporal_store(v4[e], &vals[ebase + p]);
+                        __builtin_nontemporal_store(key_of(w4[e]), &keys[ebase + p]);
+                        if (VALS) __builtin_nontemporal_store(value_of(w4[e]), &vals[ebase + p]);
                     }
                 }
             }

@@ -7,7 +7,10 @@
 //   tools/finish_bucket_bench [log2 pairs = 28] [key bytes = 4] [mode = 0] [low_bits = key bits - 16]
 //   mode 0: uniformly drawn low bits   1: four distinct low-bit values per run (crowded: every workgroup takes the ballot rounds)
 //        2: one run in 16 crowded       3: ragged (a third of the runs short: 0 .. 300 pairs)
-// Records: profiles/r06/finish_bucket_*.txt.  Not part of the product.
+//   -DFBB_SKIP_ORDER: a tuning build whose bucket kernel skips step 3 (bucket_order_walk does nothing).  Its output is WRONG -- the
+//   comparisons below report differences --: time it and count its instructions only; the difference from the normal build on the
+//   same runs is step 3's share of the kernel (profiles/r08/kernel_alone.txt).
+// Records: profiles/r06/finish_bucket_*.txt, profiles/r08/.  Not part of the product.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +19,17 @@
 #include <random>
 #include <vector>
 
+#ifdef FBB_SKIP_ORDER
+#include "bucket_order.hpp"
+namespace glu_hip
+{
+template<int BPT, typename WordT, typename EntryFn>
+__device__ void bucket_order_walk_skipped(WordT*, EntryFn)
+{
+}
+} // namespace glu_hip
+#define bucket_order_walk bucket_order_walk_skipped // (the kernel's one call of it, in the header included next)
+#endif
 #include "radix_lds_bucket.hpp"
 
 using namespace glu_hip;
